@@ -13,8 +13,13 @@ scoring overlapped on a side stream -> frozen-reference log-probs -> token GAE -
 (forward + backward + bucketed RCCL all-reduce + fused AdamW) over all minibatches.
 value = generated rollout tokens summed over ranks / max-over-ranks wall time of the K timed steps.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        torchrun --nproc-per-node N bench.py --gpus N --steps K --warmup W
+A plain run sets up, warms up, times the K steps and prints the JSON line. ``--full`` adds the
+measurements that take runs of their own: the batch-1 p50 RAG answer latency (``p50_rag_latency_s``
+and its stages; ``--steps 0 --full`` measures only that) and the ``--latency-contexts`` budgets.
+``--dump-outputs DIR`` writes what the last timed step returned (rollout tensors, metrics, a seeded
+sample of the updated trainable weights) as DIR/<name>.npy, for output-for-output comparison of two builds.
 ``python bench.py --gpus N`` with N > 1 and no torchrun environment starts the N ranks itself
 (torch.distributed.run as a child process, parallel/launch.py) and exits with their status;
 RAGTL_DIST_BACKEND=gloo rehearses N ranks on one GPU.
@@ -69,8 +74,15 @@ def main():
     ap.add_argument("--doc-words", type=int, default=48)
     ap.add_argument("--nlist", type=int, default=512)
     ap.add_argument("--nprobe", type=int, default=16)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline tokens/s does not need: the batch-1 p50 RAG answer latency "
+                         "(--latency-queries answers) and the --latency-contexts budgets; off by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="PPO mode: after the timed steps write the last timed step's outputs (rollout tokens, "
+                         "log-probs, values, rewards, advantages, returns, metrics, a seeded sample of the updated "
+                         "trainable weights) as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--latency-queries", type=int, default=16)
-    ap.add_argument("--skip-latency", action="store_true")
+    ap.add_argument("--skip-latency", action="store_true", help="with --full: leave the batch-1 latency out")
     ap.add_argument("--latency-contexts", default="",
                     help="long-context RAG answers: comma list of prompt budgets in tokens (e.g. 1024,2048,4096); "
                          "each retrieves enough documents to fill its budget and reports p50 latency + stages")
@@ -119,6 +131,12 @@ def main():
     ap.add_argument("--merged-rollout", default="on", choices=["on", "off"],
                     help="rollouts on the merged bf16 W + s*B*A copy (on) or on the unmerged LoRA K-extension (off)")
     args = ap.parse_args()
+    if args.steps < 0 or args.warmup < 0:
+        ap.error("--steps and --warmup must be >= 0")
+    if args.dump_outputs and (args.mode != "ppo" or args.steps == 0):
+        ap.error("--dump-outputs writes the headline PPO step's outputs: it needs --mode ppo and --steps >= 1")
+    if args.mode == "ppo" and not args.full and (args.steps == 0 or args.latency_contexts):
+        ap.error("the RAG answer latency measurements (--steps 0, --latency-contexts) need --full")
     if args.mode == "pipeline" and args.model == "mistral-7b" and "--model" not in sys.argv:
         args.model = "llama2-13b"
     # 256 rollouts per GPU: a decode step streams the weights once whatever the batch, so a larger
@@ -248,8 +266,9 @@ def main():
         return {"query": qs, "retrieved_docs": docs, "ground_truth": [it.ground_truth for it in items]}
 
     # ---- p50 RAG answer latency (batch 1, retrieve + generate) ----
+    # (--full only: a plain run measures the headline tokens/s alone)
     lat = None
-    if not args.skip_latency:
+    if args.full and not args.skip_latency:
         rag = RagPipeline(encoder, index, corpus.docs, policy, tok, top_k=args.top_k_docs,
                           sampling=SamplingParams(max_new_tokens=args.new_tokens, temperature=0.7, top_k=50),
                           max_prompt_tokens=args.max_prompt, max_batch=1, use_graph=not args.no_graph)
@@ -260,7 +279,7 @@ def main():
         log(f"[bench] RAG latency p50={lat['p50_s']:.3f}s p90={lat['p90_s']:.3f}s "
             f"({lat['mean_new_tokens']:.0f} new tokens) stages={lat['stage_mean_s']}")
     ctx_lat = {}
-    for L in [int(x) for x in args.latency_contexts.split(",") if x]:
+    for L in [int(x) for x in args.latency_contexts.split(",") if x] if args.full else []:
         # ~50 tokens per synthetic document: retrieve enough to fill the budget, the prompt budget
         # drops the lowest-ranked ones that do not fit
         k = max(args.top_k_docs, L // 40)
@@ -394,7 +413,43 @@ def main():
         if args.json_out:
             with open(args.json_out, "w") as f:
                 json.dump(res, f, indent=2)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, trainer, m)
     parallel.shutdown()
+
+
+# metrics of a PPO step that are results of its arithmetic (durations and rates are left out),
+# in the order of DIR/metrics.npy
+DUMP_METRICS = ("reward_mean", "reward_std", "factual_accuracy", "relevance", "conciseness", "total_loss",
+                "policy_loss", "value_loss", "entropy", "approx_kl", "clipfrac", "kl_ref_k3", "kl_ref", "kl_old_ref",
+                "kl_ref_theta_old", "behaviour_logp_gap", "rollout_engine_logp_gap", "clipfrac_first_mb", "grad_norm",
+                "skipped_steps", "rollout_tokens", "response_len")
+DUMP_PARAM_SAMPLE = 1 << 20  # trainable weights sampled into DIR/params_sample.npy (4 MB)
+
+
+def dump_outputs(path, trainer, metrics):
+    """What the last timed ``trainer.step`` handed back, as ``path/<name>.npy``: the step's metrics
+    (float64, DUMP_METRICS order), the rollout it trained on (``trainer.last_rollout``: sampled tokens
+    and lengths, sampler log-probs and values, reference log-probs, rewards, advantages, returns; float32,
+    a few hundred KB each) and a fixed seeded sample of the updated trainable weights (float32)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    ro = trainer.last_rollout
+    out = {"metrics": np.array([metrics[k] for k in DUMP_METRICS], dtype=np.float64)}
+    for name, t in (("resp_tokens", ro.resp), ("resp_len", ro.resp_len), ("old_logp", ro.old_logp),
+                    ("old_values", ro.old_values), ("ref_logp", ro.ref_logp), ("scores", ro.scores),
+                    ("advantages", ro.adv), ("returns", ro.returns)):
+        out[name] = t.detach().to("cpu", torch.float32).numpy()
+    flat = trainer.flat.data.detach()
+    n = flat.numel()
+    if n > DUMP_PARAM_SAMPLE:
+        idx = torch.randint(0, n, (DUMP_PARAM_SAMPLE,), generator=torch.Generator().manual_seed(0))
+        flat = flat[idx.sort().values.to(flat.device)]
+    out["params_sample"] = flat.to("cpu", torch.float32).numpy()
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"[bench] outputs of the last timed step -> {path} ({sum(a.nbytes for a in out.values()) / 1e6:.1f} MB)")
 
 
 def torch_profile_step(trainer, make_batch, path):
