@@ -90,6 +90,13 @@ int rt_ppo_loss(const float*, const float*, const float*, const float*, const fl
 int rt_rowdot(const void*, long, const float*, const float*, int, long, float*, hipStream_t);
 int rt_decode_update(const long*, long*, int, float*, const float*, float*, const float*, uint8_t*, int*, int*, long*,
                      int*, int64_t*, int64_t*, int, const long*, int, long, int*, const int*, hipStream_t);
+int rt_attn_verify(const void*, long, void*, void*, int, const int*, const int*, const int*, const int*, const float*,
+                   const float*, float, int, void*, long, int, int, int, int, int, float, int, hipStream_t);
+int rt_lookup_accept(const long*, const float*, const long*, const int*, int, long*, float*, int, long*, int, uint8_t*,
+                     int*, int*, int*, const int*, int*, int64_t*, int64_t*, unsigned long long*, int, const long*, int,
+                     hipStream_t);
+int rt_lookup_draft(const long*, int, const int*, const int*, const uint8_t*, int, int, long, long*, int*, uint8_t*, int,
+                    hipStream_t);
 }
 
 namespace {
@@ -1315,6 +1322,88 @@ void decode_update(const Tensor& tok, Tensor out_tokens, const optional<Tensor>&
            "decode_update");
 }
 
+// Verify step of prompt-lookup decoding: rows b * G + j of qkv are G consecutive positions of
+// sequence b (RoPE at pos0 + j, K / V appended at slot0 + j, keys < attn_len0 + j visible).
+void attn_verify(const Tensor& qkv, Tensor kc, Tensor vc, const Tensor& slot0, const Tensor& attn_len0,
+                 const optional<Tensor>& kv_start, const optional<Tensor>& pos0, const optional<Tensor>& cos,
+                 const optional<Tensor>& sin, double sign, int64_t window, double scale, int64_t Hq, int64_t G,
+                 int64_t PS, Tensor out) {
+  CHECK_CUDA(qkv); CHECK_BF16(qkv); CHECK_ROWS(qkv); CHECK_ALIGN16(qkv); CHECK_I32(slot0); CHECK_I32(attn_len0);
+  CHECK_BF16(out); CHECK_ROWS(out); CHECK_ALIGN16(out); CHECK_BF16(kc); CHECK_BF16(vc);
+  TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.is_contiguous() && vc.sizes() == kc.sizes(),
+              "attn_verify: cache layout");
+  const int64_t B = kc.size(0), Hkv = kc.size(1), Smax = kc.size(2), D = kc.size(3);
+  TORCH_CHECK(G >= 1 && G <= 8 && Hkv > 0 && Hq % Hkv == 0, "attn_verify: 1 <= G <= 8, Hq a multiple of Hkv");
+  TORCH_CHECK(qkv.size(0) == B * G && out.size(0) == B * G && slot0.numel() == B && attn_len0.numel() == B,
+              "attn_verify: batch");
+  TORCH_CHECK(qkv.size(1) >= (Hq + 2 * Hkv) * D && out.size(1) >= Hq * D, "attn_verify: widths");
+  const bool rot = cos.has_value() && cos->defined();
+  if (rot) {
+    CHECK_F32(*cos); CHECK_F32(*sin);
+    TORCH_CHECK(pos0.has_value() && pos0->defined(), "attn_verify: rotary needs pos0");
+    CHECK_I32(*pos0);
+    TORCH_CHECK(pos0->numel() == B && cos->size(-1) == D / 2 && cos->is_contiguous() && sin->is_contiguous(),
+                "attn_verify: tables");
+  }
+  if (kv_start.has_value() && kv_start->defined()) {
+    CHECK_I32(*kv_start);
+    TORCH_CHECK(kv_start->numel() == B, "attn_verify: kv_start");
+  }
+  check_rc(rt_attn_verify(qkv.data_ptr(), qkv.stride(0), kc.data_ptr(), vc.data_ptr(), (int)Smax,
+                          slot0.data_ptr<int>(), attn_len0.data_ptr<int>(), (const int*)opt_ptr(kv_start),
+                          rot ? pos0->data_ptr<int>() : nullptr, rot ? cos->data_ptr<float>() : nullptr,
+                          rot ? sin->data_ptr<float>() : nullptr, (float)sign, (int)window, out.data_ptr(),
+                          out.stride(0), (int)B, (int)G, (int)Hq, (int)Hkv, (int)D, (float)scale, (int)PS,
+                          cur_stream()),
+           "attn_verify");
+}
+
+// Bookkeeping of a verify step (csrc/kernels/rl.hip): accept the reproduced draft prefix, emit.
+void lookup_accept(const Tensor& sampled, const Tensor& logp, const Tensor& inp, const Tensor& n_draft,
+                   Tensor out_tokens, Tensor out_logp, Tensor hist, Tensor active, Tensor kv_len, Tensor pos,
+                   Tensor attn_len, const Tensor& kv_start, Tensor gen_len, Tensor step, Tensor rng_offset,
+                   Tensor counters, const Tensor& eos_ids) {
+  CHECK_CUDA(sampled); CHECK_I64(sampled); CHECK_F32(logp); CHECK_I64(inp); CHECK_I32(n_draft); CHECK_I64(out_tokens);
+  CHECK_F32(out_logp); CHECK_I64(hist); CHECK_I32(kv_len); CHECK_I32(pos); CHECK_I32(attn_len); CHECK_I32(kv_start);
+  CHECK_I32(gen_len); CHECK_I64(step); CHECK_I64(rng_offset); CHECK_I64(counters); CHECK_I64(eos_ids);
+  TORCH_CHECK(active.scalar_type() == at::kByte, "lookup_accept: active uint8");
+  TORCH_CHECK(inp.dim() == 2 && inp.is_contiguous() && sampled.is_contiguous() && logp.is_contiguous(),
+              "lookup_accept: inp [B, G]");
+  const int64_t B = inp.size(0), G = inp.size(1);
+  TORCH_CHECK(sampled.numel() == B * G && logp.numel() == B * G && n_draft.numel() >= B, "lookup_accept: [B, G]");
+  TORCH_CHECK(out_tokens.dim() == 2 && out_tokens.is_contiguous() && out_logp.is_contiguous() &&
+                  out_logp.sizes() == out_tokens.sizes() && out_tokens.size(0) >= B, "lookup_accept: outputs [B, T]");
+  TORCH_CHECK(hist.dim() == 2 && hist.is_contiguous() && hist.size(0) >= B, "lookup_accept: hist [B, Smax]");
+  TORCH_CHECK(active.numel() >= B && kv_len.numel() >= B && pos.numel() >= B && attn_len.numel() >= B &&
+                  kv_start.numel() >= B && gen_len.numel() >= B && counters.numel() >= 3, "lookup_accept: state");
+  check_rc(rt_lookup_accept((const long*)sampled.data_ptr(), logp.data_ptr<float>(), (const long*)inp.data_ptr(),
+                            n_draft.data_ptr<int>(), (int)G, (long*)out_tokens.data_ptr(), out_logp.data_ptr<float>(),
+                            (int)out_tokens.size(1), (long*)hist.data_ptr(), (int)hist.size(1),
+                            (uint8_t*)active.data_ptr(), kv_len.data_ptr<int>(), pos.data_ptr<int>(),
+                            attn_len.data_ptr<int>(), kv_start.data_ptr<int>(), gen_len.data_ptr<int>(),
+                            (int64_t*)step.data_ptr(), (int64_t*)rng_offset.data_ptr(),
+                            (unsigned long long*)counters.data_ptr(), (int)B, (const long*)eos_ids.data_ptr(),
+                            (int)eos_ids.numel(), cur_stream()),
+           "lookup_accept");
+}
+
+// The next verify step's inputs: last emitted token + the n-gram lookup draft (one workgroup per row).
+void lookup_draft(const Tensor& hist, const Tensor& kv_len, const Tensor& kv_start, const Tensor& active, int64_t ngram,
+                  int64_t pad_id, Tensor inp, Tensor n_draft, Tensor row_active) {
+  CHECK_CUDA(hist); CHECK_I64(hist); CHECK_I32(kv_len); CHECK_I32(kv_start); CHECK_I64(inp); CHECK_I32(n_draft);
+  TORCH_CHECK(active.scalar_type() == at::kByte && row_active.scalar_type() == at::kByte, "lookup_draft: uint8 flags");
+  TORCH_CHECK(inp.dim() == 2 && inp.is_contiguous() && hist.dim() == 2 && hist.is_contiguous(), "lookup_draft: layout");
+  const int64_t B = inp.size(0), G = inp.size(1);
+  TORCH_CHECK(hist.size(0) >= B && kv_len.numel() >= B && kv_start.numel() >= B && active.numel() >= B &&
+                  n_draft.numel() >= B && row_active.numel() >= B * G && row_active.is_contiguous(),
+              "lookup_draft: state");
+  check_rc(rt_lookup_draft((const long*)hist.data_ptr(), (int)hist.size(1), kv_len.data_ptr<int>(),
+                           kv_start.data_ptr<int>(), (const uint8_t*)active.data_ptr(), (int)G, (int)ngram, (long)pad_id,
+                           (long*)inp.data_ptr(), n_draft.data_ptr<int>(), (uint8_t*)row_active.data_ptr(), (int)B,
+                           cur_stream()),
+           "lookup_draft");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1402,6 +1491,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ppo_loss", &ppo_loss, "fused token-level PPO loss: {stats[9], dlp, dv, dent}");
   m.def("rowdot", &rowdot, "value head: batch-invariant per-row dot product");
   m.def("decode_update", &decode_update);
+  m.def("attn_verify", &attn_verify, "verify step: RoPE + KV append + attention of G consecutive positions per row");
+  m.def("lookup_accept", &lookup_accept, "prompt-lookup decoding: accept / emit bookkeeping of a verify step");
+  m.def("lookup_draft", &lookup_draft, "prompt-lookup decoding: next inputs = last token + n-gram draft");
   ragtl::bind_tokenizer(m);
   ragtl::bind_ivf_host(m);
 }

@@ -1554,6 +1554,506 @@ __global__ __launch_bounds__(64 * W) void attn_decode_mfma_kernel(DecodeFusedArg
 }
 
 // ---------------------------------------------------------------------------------------------
+// Verify step (prompt-lookup speculative decoding): G consecutive positions of one sequence
+// ---------------------------------------------------------------------------------------------
+// Rows b * G + j (j < G) of qkv are G consecutive positions of sequence b: position j is rotated at
+// pos0 + j, its K / V row appended at cache slot slot0 + j, and it attends to the keys
+// [max(kv_start, len_j - window), len_j), len_j = attn_len0 + j — what G successive launches of the
+// decode step above compute (contract: slot0 = attn_len0 - 1, the generator's invariant; key c is
+// cache slot c). The G * Q (position, head) pairs of a kv head (Q = Hq / Hkv, row = j * Q + head) are
+// the query rows of ceil(G Q / 16) 16-row MFMA tiles; one workgroup of W waves per (batch, kv head,
+// row tile) streams the cache row once for its 16 query rows (Mistral-7B at K = 7: 32 rows, two
+// workgroups per kv head — a plain step at 8 rows streams eight cache rows from eight workgroups).
+// Wave w takes the 16-key tiles w, w + W, ... with three tiles in flight, exactly as
+// attn_decode_mfma_kernel<G, W > 1>; the S^T / P·V MFMA fragments and the V image are that kernel's,
+// so a query row's arithmetic is that kernel's whenever the two walk the same 16-key tiles (no
+// window shorter than the sequence).
+//   * New rows: the workgroup rotates its query rows and all G new K rows (rope_chunk: the decode
+//     kernels' arithmetic, so appended rows are bitwise those of successive decode steps) into LDS
+//     and copies the G new V rows there; row tile 0 stores K / V to the cache from the same
+//     registers. Keys at or above slot0 are always taken from LDS: the launch never reads back what
+//     it appends, and a rejected draft's stale rows (slots >= slot0) are never looked at.
+//   * Masks: a score is replaced by -inf unless kbeg_j <= key < len_j (and row < G * Q) BEFORE the
+//     tile maximum; a tile with no visible key for a row leaves that row's (m, l, O) untouched
+//     (m = -inf is never exponentiated against itself). Every row sees at least its own new key.
+//   * Merge: the W waves' (m, l, O) meet in LDS (the region of their V images).
+// Long caches are walked by the one workgroup (no partitions, no workspace).
+struct VerifyArgs {
+  const bf16_t* qkv; long ldq;      // [B * G, ldq] pre-RoPE
+  bf16_t* kc; bf16_t* vc; int Smax; // [B, Hkv, Smax, D]
+  const int* slot0; const int* len0; const int* kv_start; const int* pos0;
+  const float* cosT; const float* sinT; float sign;
+  int window;
+  bf16_t* o; long ldo;              // [B * G, ldo]
+  int G, Hq, Hkv, qshift;           // G positions per sequence; Q = Hq / Hkv = 1 << qshift
+  float scale_log2;
+  int NP, PS;                       // head_dim 64 form: the decode step's key partitions (PS keys each)
+};
+
+template <int D, int W>
+__global__ __launch_bounds__(64 * W) void attn_verify_mfma_kernel(VerifyArgs a) {
+  constexpr int NT = 1;  // one 16-row query tile per workgroup (blockIdx.y)
+  constexpr int DS = D / 32, DT = D / 16, CPR = D / 8, NVL = D / 32, GMAX = 8;
+  // per wave: V image (32 rows, 16..31 zero) while streaming, then its [16][D] fp32 O rows of a merge pass
+  __shared__ __attribute__((aligned(16))) char vimg_all[W][32 * D * 2];
+  __shared__ __attribute__((aligned(16))) bf16_t qs[16 * NT * D];  // rotated query rows (zero past G * Q)
+  __shared__ __attribute__((aligned(16))) bf16_t kns[GMAX * D];    // rotated new K rows
+  __shared__ __attribute__((aligned(16))) bf16_t vns[GMAX * D];    // new V rows
+  __shared__ float mst[W][16 * NT], lst[W][16 * NT];
+  static_assert(32 * D * 2 == 16 * D * 4, "O rows of a merge pass reuse the V image");
+  const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, r16 = lane & 15, w = tid >> 6;
+  char* vimg = vimg_all[w];
+  const int b = blockIdx.x / a.Hkv, hk = blockIdx.x % a.Hkv;
+  const int G = a.G, Q = 1 << a.qshift, R = G * Q;
+  const int rbase = 16 * blockIdx.y;  // this workgroup's query rows [rbase, rbase + 16)
+  const int len0 = a.len0[b], s0 = a.slot0[b];
+  const long row0 = (long)b * G;  // first qkv / output row of the sequence
+  RT_ASSERT(s0 >= 0 && s0 + G <= a.Smax && len0 >= 1 && s0 == len0 - 1);
+  const int kstart = a.kv_start ? a.kv_start[b] : 0;
+  // keys streamed: [kbeg, len) = the union over this tile's positions (its first starts lowest)
+  int kbeg = max(kstart, 0);
+  if (a.window > 0) kbeg = max(kbeg, len0 + (rbase >> a.qshift) - a.window);
+  // (position of this tile's last row ends highest)
+  const int jlast = min(G - 1, (rbase + 15) >> a.qshift);
+  const int len = min(len0 + jlast, a.Smax);
+  const int p0 = a.pos0 ? a.pos0[b] : 0;
+  const bf16_t* kbase = a.kc + ((long)b * a.Hkv + hk) * a.Smax * D;
+  const bf16_t* vbase = a.vc + ((long)b * a.Hkv + hk) * a.Smax * D;
+
+  // tile of 16 keys from c0: K fragments k[s] = K[c0 + r16][32 s + 8 g ..]; V pieces v[i] = chunk
+  // (64 i + lane) % CPR of key c0 + (64 i + lane) / CPR. Keys past len - 1 re-read slot len - 1.
+  struct Tile { uint4 k[DS]; uint4 v[NVL]; };
+  auto load = [&](Tile& T, int c0) {
+    const long keyk = max(min(c0 + r16, len - 1), 0);
+#pragma unroll
+    for (int s2 = 0; s2 < DS; ++s2) T.k[s2] = load_nt16(kbase + keyk * D + 32 * s2 + 8 * g);
+#pragma unroll
+    for (int i = 0; i < NVL; ++i) {
+      const int f = 64 * i + lane;
+      const long key = max(min(c0 + f / CPR, len - 1), 0);
+      T.v[i] = load_nt16(vbase + key * D + 8 * (f % CPR));
+    }
+  };
+  Tile ta, tb, tc;
+  const int cfirst = kbeg + 16 * w, cstep = 16 * W;
+  if (cfirst < len) load(ta, cfirst);
+  if (cfirst + cstep < len) load(tb, cfirst + cstep);
+  if (cfirst + 2 * cstep < len) load(tc, cfirst + 2 * cstep);
+
+  // ---- rotate q rows and new K rows into LDS, copy new V rows; append K / V to the cache ----
+  {
+    DecodeFusedArgs ra;
+    ra.cosT = a.cosT; ra.sinT = a.sinT; ra.sign = a.sign;
+    constexpr int NQ = 16 * NT * CPR, NKV = GMAX * CPR;
+    for (int ch = tid; ch < NQ + 2 * NKV; ch += 64 * W) {
+      uint4 val = make_uint4(0, 0, 0, 0);
+      if (ch < NQ) {
+        const int row = rbase + ch / CPR, dl = ch % CPR;
+        if (row < R) {
+          const int j = row >> a.qshift, hq = row & (Q - 1);
+          float f[8];
+          rope_chunk<D>(a.qkv + (row0 + j) * a.ldq + (long)(hk * Q + hq) * D, dl, ra, p0 + j, f);
+          val = pack8(f);
+        }
+        *(uint4*)(qs + (row - rbase) * D + dl * 8) = val;
+      } else {
+        const int c2 = ch - NQ;
+        const bool isv = c2 >= NKV;
+        const int j = (isv ? c2 - NKV : c2) / CPR, dl = c2 % CPR;
+        if (j < G) {
+          const bf16_t* src = a.qkv + (row0 + j) * a.ldq;
+          if (isv) {
+            val = *(const uint4*)(src + (long)(a.Hq + a.Hkv + hk) * D + dl * 8);
+          } else {
+            float f[8];
+            rope_chunk<D>(src + (long)(a.Hq + hk) * D, dl, ra, p0 + j, f);
+            val = pack8(f);
+          }
+          if (blockIdx.y == 0 && s0 >= 0 && s0 + j < a.Smax) {
+            bf16_t* dst = (isv ? a.vc : a.kc) + (((long)b * a.Hkv + hk) * a.Smax + s0 + j) * D + dl * 8;
+            *(uint4*)dst = val;
+          }
+        }
+        *(uint4*)((isv ? vns : kns) + j * D + dl * 8) = val;
+      }
+    }
+  }
+  // P·V runs K = 32 MFMAs on 16-key tiles: k-slots 4..7 carry P = 0 against zero V rows 16..31
+#pragma unroll
+  for (int i = 0; i < NVL; ++i) {
+    const int f = 64 * i + lane;
+    *(uint4*)(vimg + v_off<D>(16 + f / CPR, f % CPR)) = make_uint4(0, 0, 0, 0);
+  }
+  __syncthreads();
+
+  // visible keys [klo, khi) of this lane's query row of every row tile (row 16 t + r16)
+  int klo[NT], khi[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int row = rbase + 16 * t + r16, j = row >> a.qshift;
+    const int lj = len0 + j;
+    int lo = kstart;
+    if (a.window > 0) lo = max(lo, lj - a.window);
+    klo[t] = row < R ? lo : 0;
+    khi[t] = row < R ? min(min(lj, s0 + j + 1), len) : 0;  // new row i (key s0 + i) only for i <= j
+  }
+  f32x4 o[NT][DT];
+  float m[NT], l[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    m[t] = -INFINITY;
+    l[t] = 0.f;
+#pragma unroll
+    for (int c = 0; c < DT; ++c) o[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+
+  bf16x8 qf[DS];  // B operand of S^T = K·Q^T: Q[row r16][32 s + 8 g ..]
+#pragma unroll
+  for (int s2 = 0; s2 < DS; ++s2) qf[s2] = *(const bf16x8*)(qs + r16 * D + 32 * s2 + 8 * g);
+
+  auto consume = [&](Tile& T, int c0) {
+    uint4 kf[DS], vf[NVL];
+#pragma unroll
+    for (int s2 = 0; s2 < DS; ++s2) kf[s2] = T.k[s2];
+#pragma unroll
+    for (int i = 0; i < NVL; ++i) vf[i] = T.v[i];
+    if (c0 + 16 > s0) {
+      // keys at or above slot0 are this launch's new rows: from LDS, never from the cache
+      const int jk = min(c0 + r16, len - 1) - s0;
+      if (jk >= 0 && jk < G) {
+#pragma unroll
+        for (int s2 = 0; s2 < DS; ++s2) kf[s2] = *(const uint4*)(kns + jk * D + 32 * s2 + 8 * g);
+      }
+#pragma unroll
+      for (int i = 0; i < NVL; ++i) {
+        const int f = 64 * i + lane;
+        const int key = c0 + f / CPR, jv = min(key, len - 1) - s0;
+        if (jv >= 0 && jv < G) vf[i] = *(const uint4*)(vns + jv * D + 8 * (f % CPR));
+        if (key >= len) vf[i] = make_uint4(0, 0, 0, 0);  // P = 0 there: keep 0 * V finite
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < NVL; ++i) {
+      const int f = 64 * i + lane;
+      *(uint4*)(vimg + v_off<D>(f / CPR, f % CPR)) = vf[i];
+    }
+    bf16x8 pa[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      // S^T: lane holds the scores of keys c0 + 4 g + i for query row 16 t + r16
+      f32x4 st = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s2 = 0; s2 < DS; ++s2)
+        st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf[s2]), qf[s2], st, 0, 0, 0);
+      float mx = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int key = c0 + 4 * g + i;
+        const float x = (key >= klo[t] && key < khi[t]) ? st[i] * a.scale_log2 : -INFINITY;
+        st[i] = x;
+        mx = fmaxf(mx, x);
+      }
+      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      const float mn = fmaxf(m[t], mx);
+      const float ms = mn == -INFINITY ? 0.f : mn;  // nothing visible yet: every exponent below is -inf
+      const float alpha = exp2f(m[t] - ms);         // m = -inf: 0 (O and l are still 0)
+      m[t] = mn;
+      float rs = 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float pv = exp2f(st[i] - ms);
+        st[i] = pv;
+        rs += pv;
+      }
+      rs += __shfl_xor(rs, 16, 64);
+      rs += __shfl_xor(rs, 32, 64);
+      l[t] = l[t] * alpha + rs;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float al = __shfl(alpha, 4 * g + i, 64);
+#pragma unroll
+        for (int c = 0; c < DT; ++c) o[t][c][i] *= al;
+      }
+      pa[t] = pack_bf16x8(st, f32x4{0.f, 0.f, 0.f, 0.f});
+    }
+    // O += P·V: P (A operand) = the packed S^T accumulators, V (B operand) by transposed reads
+    const int qrow_ = lane >> 2 & 3, pcol = lane & 3;
+#pragma unroll
+    for (int c = 0; c < DT; ++c) {
+      const int key_a = 4 * g + qrow_, col = 16 * c + 4 * pcol;
+      const s16x4 lo = ds_tr16(vimg + v_off<D>(key_a, col >> 3) + ((col & 7) << 1));
+      const s16x4 hi = ds_tr16(vimg + v_off<D>(key_a + 16, col >> 3) + ((col & 7) << 1));
+      const bf16x8 vfr = cat_tr(lo, hi);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) o[t][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa[t], vfr, o[t][c], 0, 0, 0);
+    }
+  };
+
+  for (int c0 = cfirst; c0 < len; c0 += 3 * cstep) {
+    consume(ta, c0);
+    if (c0 + 3 * cstep < len) load(ta, c0 + 3 * cstep);
+    if (c0 + cstep < len) {
+      consume(tb, c0 + cstep);
+      if (c0 + 4 * cstep < len) load(tb, c0 + 4 * cstep);
+    }
+    if (c0 + 2 * cstep < len) {
+      consume(tc, c0 + 2 * cstep);
+      if (c0 + 5 * cstep < len) load(tc, c0 + 5 * cstep);
+    }
+  }
+
+  // ---- merge the W waves' states, one row tile per pass (m = -inf, l = 0 for a wave without tiles).
+  // A wave's O rows go to its own V-image region (its transposed reads precede them in its LDS queue)
+  if (g == 0) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      mst[w][16 * t + r16] = m[t];
+      lst[w][16 * t + r16] = l[t];
+    }
+  }
+  float* ost = (float*)vimg_all[0];  // [W][16][D]
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    if (t > 0) __syncthreads();  // the previous pass has been read
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int c = 0; c < DT; ++c) ost[(w * 16 + 4 * g + i) * D + 16 * c + r16] = o[t][c][i];
+    }
+    __syncthreads();
+    for (int e = tid; e < 16 * D; e += 64 * W) {
+      const int h = e / D, d = e % D, row = 16 * t + h;
+      if (rbase + row >= R) continue;
+      float M = -INFINITY;
+#pragma unroll
+      for (int q = 0; q < W; ++q) M = fmaxf(M, mst[q][row]);
+      float L = 0.f, O = 0.f;
+      if (M != -INFINITY) {
+#pragma unroll
+        for (int q = 0; q < W; ++q) {
+          const float mq = mst[q][row];
+          if (mq == -INFINITY) continue;
+          const float f = exp2f(mq - M);
+          L += lst[q][row] * f;
+          O += ost[(q * 16 + h) * D + d] * f;
+        }
+      }
+      const int j = (rbase + row) >> a.qshift, hq = (rbase + row) & (Q - 1);
+      a.o[(row0 + j) * a.ldo + (long)(hk * Q + hq) * D + d] = f2bf(L > 0.f ? O / L : 0.f);
+    }
+  }
+}
+
+// Head dims the decode step runs on attn_decode_fused_kernel (D = 64: the tiny presets): the verify
+// step is that kernel's arithmetic, position by position, in one launch. Workgroup (j, kv head,
+// batch) walks position j's keys [kbeg_j, len_j) with the decode kernel's own chunk loads, chunk
+// consumption (consume_chunk), lane / wave merges and partition merge (partitions of a.PS keys,
+// walked in order by the one workgroup and merged with the last arriver's formulas), so its output
+// is bitwise that of the j-th of G successive decode steps, and greedy verify output is greedy
+// decode output, token for token. The new rows 0..j are rotated by the workgroup itself into LDS
+// (rope_chunk) and substituted into the loaded chunks by clamped key, as consume_chunk does for its
+// one new row: nothing the launch appends is read back. Workgroup j alone stores row j. The cache row
+// is read G times here (from L2 after the first): these shapes are test-sized, the streamed-once
+// form is the MFMA kernel above.
+template <int D, int G, int NK>
+__global__ __launch_bounds__(256) void attn_verify_valu_kernel(VerifyArgs a) {
+  constexpr int LPK = D / 8, KPW = 64 / LPK, CH = 4 * KPW * NK, GMAX = 8;
+  constexpr int EPT = (G * D + 255) / 256;
+  __shared__ float red[4 * G * D];
+  __shared__ float wst[4][G][2];
+  __shared__ __attribute__((aligned(16))) bf16_t kns[GMAX * D];
+  __shared__ __attribute__((aligned(16))) bf16_t vns[GMAX * D];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int j = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
+  const int s0 = a.slot0[b], len = min(a.len0[b] + j, a.Smax);
+  const int s_new = s0 + j;
+  RT_ASSERT(s0 >= 0 && s0 + a.G <= a.Smax && a.len0[b] >= 1 && s0 == a.len0[b] - 1);
+  int kbeg = a.kv_start ? a.kv_start[b] : 0;
+  if (a.window > 0) kbeg = max(kbeg, len - a.window);
+  const int sub = lane / LPK, dl = lane % LPK;
+  const int p = (a.pos0 ? a.pos0[b] : 0) + j;
+  const bf16_t* row = a.qkv + ((long)b * a.G + j) * a.ldq;
+  const bf16_t* kbase = a.kc + ((long)b * a.Hkv + hk) * a.Smax * D;
+  const bf16_t* vbase = a.vc + ((long)b * a.Hkv + hk) * a.Smax * D;
+  DecodeFusedArgs ra;
+  ra.cosT = a.cosT; ra.sinT = a.sinT; ra.sign = a.sign;
+  // new rows 0..j -> LDS (thread = one 8-element chunk of one row's K or V); row j -> cache
+  if (tid < 2 * GMAX * LPK) {
+    const bool isv = tid >= GMAX * LPK;
+    const int i = (isv ? tid - GMAX * LPK : tid) / LPK, c = tid % LPK;
+    uint4 val = make_uint4(0, 0, 0, 0);
+    if (i <= j) {
+      const bf16_t* src = a.qkv + ((long)b * a.G + i) * a.ldq;
+      if (isv) {
+        val = *(const uint4*)(src + (long)(a.Hq + a.Hkv + hk) * D + c * 8);
+      } else {
+        float kn[8];
+        rope_chunk<D>(src + (long)(a.Hq + hk) * D, c, ra, p - j + i, kn);
+        val = pack8(kn);
+      }
+      if (i == j && s_new >= 0 && s_new < a.Smax)
+        *(uint4*)((isv ? a.vc : a.kc) + (((long)b * a.Hkv + hk) * a.Smax + s_new) * D + c * 8) = val;
+    }
+    *(uint4*)((isv ? vns : kns) + i * D + c * 8) = val;
+  }
+  float qv[G][8];
+#pragma unroll
+  for (int gg = 0; gg < G; ++gg) rope_chunk<D>(row + (long)(hk * G + gg) * D, dl, ra, p, qv[gg]);
+  __syncthreads();
+
+  float Mr[EPT], Lr[EPT], Or[EPT];
+#pragma unroll
+  for (int x = 0; x < EPT; ++x) { Mr[x] = -INFINITY; Lr[x] = 0.f; Or[x] = 0.f; }
+  const uint4 zero4 = make_uint4(0, 0, 0, 0);
+  for (int part = 0; part < a.NP; ++part) {
+    const int p0 = max(part * a.PS, kbeg), p1 = min((part + 1) * a.PS, len);
+    const bool active = p0 < p1;
+    float mrow[G], lrow[G];
+    if (active) {
+      // keys at or above slot0 (clamped index, as the loads) are this launch's new rows: from LDS
+      auto subst = [&](KVChunk<D, NK>& c, int c0) {
+        if (c0 + CH <= s0 && p1 - 1 < s0) return;
+#pragma unroll
+        for (int i = 0; i < NK; ++i) {
+          const int jn = min(c0 + (i * 4 + wid) * KPW + sub, p1 - 1) - s0;
+          if (jn >= 0 && jn <= j) {
+            c.k[i] = *(const uint4*)(kns + jn * D + dl * 8);
+            c.v[i] = *(const uint4*)(vns + jn * D + dl * 8);
+          }
+        }
+      };
+      KVChunk<D, NK> ca, cb;
+      load_chunk<D, NK>(ca, kbase, vbase, p0, p1, wid, sub, dl, true);
+      if (p0 + CH < p1) load_chunk<D, NK>(cb, kbase, vbase, p0 + CH, p1, wid, sub, dl, true);
+      float m[G], l[G], acc[G][8];
+#pragma unroll
+      for (int gg = 0; gg < G; ++gg) {
+        m[gg] = -INFINITY;
+        l[gg] = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[gg][e] = 0.f;
+      }
+      for (int c0 = p0; c0 < p1; c0 += 2 * CH) {
+        if (c0 != p0 && c0 + CH < p1) load_chunk<D, NK>(cb, kbase, vbase, c0 + CH, p1, wid, sub, dl, true);
+        subst(ca, c0);
+        consume_chunk<D, G, NK>(ca, c0, p1, s_new, false, zero4, zero4, qv, m, l, acc, wid, sub, a.scale_log2);
+        if (c0 + CH < p1) {
+          if (c0 + 2 * CH < p1) load_chunk<D, NK>(ca, kbase, vbase, c0 + 2 * CH, p1, wid, sub, dl, true);
+          subst(cb, c0 + CH);
+          consume_chunk<D, G, NK>(cb, c0 + CH, p1, s_new, false, zero4, zero4, qv, m, l, acc, wid, sub,
+                                  a.scale_log2);
+        }
+      }
+      // the decode kernel's merges: over sub within the wave, then over the 4 waves
+#pragma unroll
+      for (int gg = 0; gg < G; ++gg) {
+        float mw = m[gg];
+#pragma unroll
+        for (int off = LPK; off < 64; off <<= 1) mw = fmaxf(mw, __shfl_xor(mw, off, 64));
+        const float r = (m[gg] == -INFINITY) ? 0.f : exp2f(m[gg] - mw);
+        l[gg] *= r;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[gg][e] *= r;
+        m[gg] = mw;
+        if (lane == 0) wst[wid][gg][0] = mw;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int gg = 0; gg < G; ++gg) {
+        mrow[gg] = fmaxf(fmaxf(wst[0][gg][0], wst[1][gg][0]), fmaxf(wst[2][gg][0], wst[3][gg][0]));
+        const float r = (m[gg] == -INFINITY) ? 0.f : exp2f(m[gg] - mrow[gg]);
+        float lsum = l[gg] * r;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[gg][e] *= r;
+#pragma unroll
+        for (int off = LPK; off < 64; off <<= 1) {
+          lsum += __shfl_xor(lsum, off, 64);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[gg][e] += __shfl_xor(acc[gg][e], off, 64);
+        }
+        if (sub == 0) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) red[(wid * G + gg) * D + dl * 8 + e] = acc[gg][e];
+        }
+        if (lane == 0) wst[wid][gg][1] = lsum;
+      }
+      __syncthreads();
+#pragma unroll
+      for (int gg = 0; gg < G; ++gg) lrow[gg] = wst[0][gg][1] + wst[1][gg][1] + wst[2][gg][1] + wst[3][gg][1];
+    }
+#pragma unroll
+    for (int x = 0; x < EPT; ++x) {
+      const int e = tid + 256 * x;
+      if (e >= G * D) continue;
+      const int gg = e / D, d = e % D;
+      const float osum = active ? red[(0 * G + gg) * D + d] + red[(1 * G + gg) * D + d] + red[(2 * G + gg) * D + d] +
+                                      red[(3 * G + gg) * D + d]
+                                : 0.f;
+      float mq = -INFINITY, lq = 0.f;
+#pragma unroll
+      for (int g2 = 0; g2 < G; ++g2)
+        if (g2 == gg && active) { mq = mrow[g2]; lq = lrow[g2]; }
+      if (a.NP == 1) {  // the decode kernel's single-partition store
+        Or[x] = (active && lq > 0.f) ? osum / lq : 0.f;
+        Lr[x] = -1.f;
+      } else if (mq != -INFINITY) {  // its last arriver's merge, partitions in order
+        const float Mn = fmaxf(Mr[x], mq);
+        const float r0 = exp2f(Mr[x] - Mn), r1 = exp2f(mq - Mn);
+        Lr[x] = Lr[x] * r0 + lq * r1;
+        Or[x] = Or[x] * r0 + osum * r1;
+        Mr[x] = Mn;
+      }
+    }
+    __syncthreads();  // red / wst are rewritten by the next partition
+  }
+#pragma unroll
+  for (int x = 0; x < EPT; ++x) {
+    const int e = tid + 256 * x;
+    if (e >= G * D) continue;
+    const int gg = e / D, d = e % D;
+    const float ov = Lr[x] == -1.f ? Or[x] : (Lr[x] > 0.f ? Or[x] / Lr[x] : 0.f);
+    a.o[((long)b * a.G + j) * a.ldo + (long)(hk * G + gg) * D + d] = f2bf(ov);
+  }
+}
+
+extern "C" int rt_attn_verify(const void* qkv, long ldq, void* kc, void* vc, int Smax, const int* slot0,
+                              const int* len0, const int* kv_start, const int* pos0, const float* cosT,
+                              const float* sinT, float sign, int window, void* o, long ldo, int B, int G, int Hq,
+                              int Hkv, int D, float scale, int PS, hipStream_t stream) {
+  // PS: keys per partition of the decode step's workspace (head_dim 64 only: same partitions, same sums)
+  if (B == 0) return 0;
+  const int Q = Hkv ? Hq / Hkv : 0;
+  if (Q * Hkv != Hq || (Q != 1 && Q != 2 && Q != 4 && Q != 8) || G < 1 || G > 8) return -1;
+  if ((D != 64 && D != 128) || ldq % 8 || ldo % 8 || Smax < G) return -1;
+  VerifyArgs a;
+  a.qkv = (const bf16_t*)qkv; a.ldq = ldq; a.kc = (bf16_t*)kc; a.vc = (bf16_t*)vc; a.Smax = Smax;
+  a.slot0 = slot0; a.len0 = len0; a.kv_start = kv_start; a.pos0 = pos0; a.cosT = cosT; a.sinT = sinT; a.sign = sign;
+  a.window = window; a.o = (bf16_t*)o; a.ldo = ldo; a.G = G; a.Hq = Hq; a.Hkv = Hkv;
+  a.qshift = Q == 1 ? 0 : Q == 2 ? 1 : Q == 4 ? 2 : 3;
+  a.scale_log2 = scale * 1.4426950408889634f;
+  a.NP = 1; a.PS = Smax;
+  if (D == 64) {
+    if (PS <= 0 || PS % (4 * (64 / (D / 8)) * 4) != 0) return -1;
+    a.PS = PS; a.NP = (Smax + PS - 1) / PS;
+    dim3 vgrid((unsigned)G, (unsigned)Hkv, (unsigned)B);
+    switch (Q) {
+      case 1: hipLaunchKernelGGL((attn_verify_valu_kernel<64, 1, 4>), vgrid, dim3(256), 0, stream, a); break;
+      case 2: hipLaunchKernelGGL((attn_verify_valu_kernel<64, 2, 4>), vgrid, dim3(256), 0, stream, a); break;
+      case 4: hipLaunchKernelGGL((attn_verify_valu_kernel<64, 4, 4>), vgrid, dim3(256), 0, stream, a); break;
+      default: hipLaunchKernelGGL((attn_verify_valu_kernel<64, 8, 4>), vgrid, dim3(256), 0, stream, a); break;
+    }
+    RT_LAUNCH_CHECK();
+    return 0;
+  }
+  // 8 waves per (batch, kv head, 16-row query tile), as the decode kernel's small-batch form
+  dim3 grid((unsigned)(B * Hkv), (unsigned)((G * Q + 15) / 16));
+  hipLaunchKernelGGL((attn_verify_mfma_kernel<128, 8>), grid, dim3(64 * 8), 0, stream, a);
+  RT_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------------------------
 struct AttnBwdArgs {

@@ -142,6 +142,143 @@ __global__ void decode_update_kernel(const long* __restrict__ tok, long* __restr
   }
 }
 
+// Prompt-lookup speculative decoding, bookkeeping of a verify step (G = K + 1 positions per row).
+// `inp` [B, G] held the step's inputs (last emitted token | K draft tokens, n_draft[b] of them real),
+// `sampled` / `logp` [B, G] what the sampler drew after each of them. An active row accepts the
+// longest prefix a of its draft that the sampler reproduced and emits sampled[0..a], cut after the
+// first EOS and at the output width; tokens and log-probs go to the row's own output position, the
+// tokens also into the history `hist` [B, Smax] (indexed like cache slots: the last emitted token
+// sits at hist[kv_len], the slot the next step appends it at). Lengths advance by the emitted count.
+// counters: {row-steps, drafted tokens, accepted tokens that were emitted} (integer atomics: the sum
+// does not depend on thread order). One thread per row, one workgroup.
+__global__ void lookup_accept_kernel(const long* __restrict__ sampled, const float* __restrict__ logp,
+                                     const long* __restrict__ inp, const int* __restrict__ n_draft, int G,
+                                     long* __restrict__ out_tokens, float* __restrict__ out_logp, int max_new,
+                                     long* __restrict__ hist, int Smax, uint8_t* __restrict__ active,
+                                     int* __restrict__ kv_len, int* __restrict__ pos, int* __restrict__ attn_len,
+                                     const int* __restrict__ kv_start, int* __restrict__ gen_len,
+                                     int64_t* __restrict__ step, int64_t* __restrict__ rng_offset,
+                                     unsigned long long* __restrict__ counters, int B,
+                                     const long* __restrict__ eos_ids, int n_eos) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t s = *step;
+  if (b < B) {
+    const int gl = gen_len[b], kl = kv_len[b];
+    if (active[b] != 0 && gl < max_new) {
+      const int nd = min(max(n_draft[b], 0), G - 1);
+      int a = 0;
+      while (a < nd && sampled[(long)b * G + a] == inp[(long)b * G + a + 1]) ++a;
+      int e = 0;
+      bool fin = false;
+      for (int i = 0; i <= a && !fin; ++i) {
+        const long t = sampled[(long)b * G + i];
+        out_tokens[(long)b * max_new + gl + i] = t;
+        out_logp[(long)b * max_new + gl + i] = logp[(long)b * G + i];
+        if (kl + 1 + i < Smax) hist[(long)b * Smax + kl + 1 + i] = t;
+        e = i + 1;
+        fin = gl + e >= max_new;
+        for (int q = 0; q < n_eos; ++q) fin = fin || (t == eos_ids[q]);
+      }
+      gen_len[b] = gl + e;
+      kv_len[b] = kl + e;
+      if (fin) active[b] = 0;
+      atomicAdd(counters + 0, 1ull);
+      atomicAdd(counters + 1, (unsigned long long)nd);
+      atomicAdd(counters + 2, (unsigned long long)(e - 1));
+    }
+    const int kn = kv_len[b];
+    attn_len[b] = kn + 1;
+    pos[b] = kn - (kv_start ? kv_start[b] : 0);
+  }
+  __syncthreads();
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    *step = s + 1;
+    *rng_offset = *rng_offset + 1;
+  }
+}
+
+// The next verify step's inputs of row b = blockIdx.x: inp[b, 0] = the last emitted token
+// hist[b, kv_len]; inp[b, 1..K] = the draft. With end = kv_len + 1 tokens of history, for n = ngram
+// .. 1 the latest start i in [kv_start, end - n) with hist[i .. i + n) == hist[end - n .. end) wins
+// (so at least one token follows it) and the up-to-K tokens after the match are proposed; n_draft =
+// how many exist (0: nothing matched), the rest is pad. The latest start is a max-reduction over
+// the candidates (block_max over per-thread maxima: independent of thread order). row_active
+// [B, G] = the row's active flag per position (the sampler's row mask). Inactive rows get pad.
+__global__ __launch_bounds__(256) void lookup_draft_kernel(const long* __restrict__ hist, int Smax,
+                                                           const int* __restrict__ kv_len,
+                                                           const int* __restrict__ kv_start,
+                                                           const uint8_t* __restrict__ active, int G, int ngram,
+                                                           long pad_id, long* __restrict__ inp,
+                                                           int* __restrict__ n_draft,
+                                                           uint8_t* __restrict__ row_active) {
+  __shared__ int red[4];
+  __shared__ int best_sh;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const bool act = active[b] != 0;
+  const long* h = hist + (long)b * Smax;
+  long* in = inp + (long)b * G;
+  if (tid < G) row_active[(long)b * G + tid] = act ? 1 : 0;
+  const int kl = kv_len[b];
+  if (!act || kl < 0 || kl >= Smax) {  // uniform over the workgroup
+    if (tid < G) in[tid] = pad_id;
+    if (tid == 0) n_draft[b] = 0;
+    return;
+  }
+  const int end = kl + 1, ks = max(kv_start ? kv_start[b] : 0, 0);
+  int best = -1, bn = 0;
+  for (int n = ngram; n >= 1 && best < 0; --n) {
+    int loc = -1;
+    if (end - n > ks) {
+      for (int i = ks + tid; i < end - n; i += blockDim.x) {
+        bool eq = true;
+        for (int k = 0; k < n; ++k) eq = eq && (h[i + k] == h[end - n + k]);
+        if (eq) loc = i;  // ascending i: the thread's latest
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) loc = max(loc, __shfl_xor(loc, off, 64));
+    if ((tid & 63) == 0) red[tid >> 6] = loc;
+    __syncthreads();
+    if (tid == 0) best_sh = max(max(red[0], red[1]), max(red[2], red[3]));
+    __syncthreads();
+    best = best_sh;
+    bn = n;
+    __syncthreads();  // red / best_sh are rewritten by the next n
+  }
+  const int cont = best + bn;  // first proposed token
+  const int avail = best >= 0 ? min(G - 1, end - cont) : 0;
+  if (tid == 0) {
+    in[0] = h[kl];
+    n_draft[b] = avail;
+  }
+  if (tid >= 1 && tid < G) in[tid] = tid - 1 < avail ? h[cont + tid - 1] : pad_id;
+}
+
+extern "C" int rt_lookup_accept(const long* sampled, const float* logp, const long* inp, const int* n_draft, int G,
+                                long* out_tokens, float* out_logp, int max_new, long* hist, int Smax,
+                                uint8_t* active, int* kv_len, int* pos, int* attn_len, const int* kv_start,
+                                int* gen_len, int64_t* step, int64_t* rng_offset, unsigned long long* counters, int B,
+                                const long* eos_ids, int n_eos, hipStream_t stream) {
+  if (B > 1024 || G < 1 || G > 8) return -1;
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(lookup_accept_kernel, dim3(1), dim3(((B + 63) / 64) * 64), 0, stream, sampled, logp, inp,
+                     n_draft, G, out_tokens, out_logp, max_new, hist, Smax, active, kv_len, pos, attn_len, kv_start,
+                     gen_len, step, rng_offset, counters, B, eos_ids, n_eos);
+  RT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int rt_lookup_draft(const long* hist, int Smax, const int* kv_len, const int* kv_start,
+                               const uint8_t* active, int G, int ngram, long pad_id, long* inp, int* n_draft,
+                               uint8_t* row_active, int B, hipStream_t stream) {
+  if (G < 1 || G > 8 || ngram < 1) return -1;
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(lookup_draft_kernel, dim3((unsigned)B), dim3(256), 0, stream, hist, Smax, kv_len, kv_start,
+                     active, G, ngram, pad_id, inp, n_draft, row_active);
+  RT_LAUNCH_CHECK();
+  return 0;
+}
+
 // Token-level PPO objective over [B, T] (masked mean over the n response tokens), forward AND its
 // closed-form gradient in one single-workgroup launch (a minibatch holds a few thousand tokens):
 //   pg   = mean(-min(r A, clip(r, 1 +- eps) A)),  r = exp(lp - old)

@@ -139,7 +139,8 @@ def cmd_rag(cfg, args):
     st = build_stack(cfg, di.device)
     _apply_fp8(cfg, st["policy"])
     sp = SamplingParams(max_new_tokens=cfg.ppo.max_new_tokens, temperature=cfg.eval.temperature,
-                        do_sample=cfg.eval.do_sample, top_k=cfg.eval.top_k)
+                        do_sample=cfg.eval.do_sample, top_k=cfg.eval.top_k, lookup_tokens=cfg.eval.lookup_tokens,
+                        lookup_ngram=cfg.eval.lookup_ngram)
     rag = RagPipeline(st["encoder"], st["index"], st["docs"], st["policy"], st["tokenizer"], cfg.retrieval.top_k, sp,
                       cfg.ppo.max_prompt_tokens)
     queries = args.query or [it.query for it in st["corpus"].sample_queries(4)] if st["corpus"] else args.query

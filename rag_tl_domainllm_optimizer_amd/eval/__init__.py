@@ -36,6 +36,9 @@ class EvalConfig:
     # ``cli pipeline`` ends with the reference's model comparison (rl.py:444-463, 491-525) over this
     # many held-out queries (0 disables it)
     compare_items: int = 32
+    # prompt-lookup speculative decoding of the answers (SamplingParams.lookup_tokens / lookup_ngram)
+    lookup_tokens: int = 0
+    lookup_ngram: int = 2
 
 
 class Evaluator:
@@ -60,9 +63,9 @@ class Evaluator:
                 prompts.append(ids[-(c.max_length - 1):])
         S = max(len(p) for p in prompts)
         T = max(1, min(c.max_new_tokens, c.max_length - S))
-        gen = Generator(model, min(c.batch_size, len(prompts)), S + T + 1)
+        gen = Generator(model, min(c.batch_size, len(prompts)), S + T + 1 + c.lookup_tokens)
         params = SamplingParams(max_new_tokens=T, temperature=c.temperature, top_k=c.top_k, do_sample=c.do_sample,
-                                seed=c.seed)
+                                seed=c.seed, lookup_tokens=c.lookup_tokens, lookup_ngram=c.lookup_ngram)
         out_txt = []
         for s in range(0, len(prompts), gen.max_batch):
             o = gen.generate(prompts[s:s + gen.max_batch], params, pad_id=tokenizer.pad_token_id,

@@ -31,6 +31,11 @@ class SamplingParams:
     max_length: Optional[int] = None    # reference semantics: prompt + new tokens (rl.py:40)
     stop_token_ids: Sequence[int] = ()
     seed: int = 0
+    # prompt-lookup speculative decoding (batch-1..8 RAG answers): K draft tokens per step, proposed
+    # from the sequence's own history (the tokens after the latest earlier occurrence of its last
+    # n-gram, n = lookup_ngram .. 1) and verified in one forward over K + 1 positions. 0: off
+    lookup_tokens: int = 0
+    lookup_ngram: int = 2
 
     @property
     def greedy(self) -> bool:
@@ -164,6 +169,11 @@ class Generator:
         self.values = torch.zeros(B, dtype=torch.float32, device=dev)
         self.out_tokens = None
         self.runner = _GraphSet()  # captured decode steps (runtime.GraphRunner each, shared graph pool)
+        # prompt-lookup decoding: token history (indexed like cache slots) and, per K, the verify
+        # step's static buffers — allocated on first use, untouched when lookup_tokens == 0
+        self.hist = None
+        self._lookup = {}
+        self._lk = None
 
     # ------------------------------------------------------------------ one decode step (device only)
     def _bucket(self, B: int) -> int:
@@ -183,6 +193,51 @@ class Generator:
         h = self.model.decode(self.tok_in[:nb], self.pos[:nb], self.kv_len[:nb], self.attn_len[:nb],
                               self.kv_start[:nb], cache, self.workspace)
         self._emit(h, params, eos_ids, pad_id)
+
+    def _lookup_buffers(self, K: int) -> "_LookupState":
+        if self.hist is None:
+            self.hist = torch.zeros(self.max_batch, self.max_seq, dtype=torch.long, device=self.device)
+        st = self._lookup.get(K)
+        if st is None:
+            st = self._lookup[K] = _LookupState(self.max_batch, K + 1, self.device)
+        return st
+
+    def _check_lookup(self, params: SamplingParams):
+        K, n = params.lookup_tokens, params.lookup_ngram
+        if not 0 <= K <= 7:
+            raise ValueError(f"lookup_tokens = {K}: supported 0..7 draft tokens per step")
+        if K == 0:
+            return
+        if n < 1:
+            raise ValueError(f"lookup_ngram = {n}: must be >= 1")
+        if self.cache.fp8:
+            raise NotImplementedError("prompt-lookup decoding does not support the fp8 K/V cache")
+        if self.cfg.arch == "opt":
+            raise NotImplementedError("prompt-lookup decoding does not support learned-position (opt) models")
+        if self.value_head is not None:
+            raise NotImplementedError("prompt-lookup decoding does not support a value head (PPO rollouts)")
+
+    def _step_verify(self, params: SamplingParams, eos_ids: torch.Tensor, pad_id: int):
+        """One verify step: forward over G = K + 1 positions per row (the last emitted token and the
+        draft), the ordinary sampler on every position, then the accept and draft bookkeeping."""
+        nb, st = self._nb, self._lk
+        G = st.G
+        cache = self.cache if nb == self.max_batch else _SubCache(self.cache, nb)
+        h = self.model.decode_verify(st.inp[:nb], self.pos[:nb], self.kv_len[:nb], self.attn_len[:nb],
+                                     self.kv_start[:nb], cache, self.workspace)
+        logits = self.model.logits(h)
+        ops.sample(logits, params.inv_temp, params.top_k, params.top_p, params.greedy, params.seed,
+                   self.rng_offset, st.row_active[:nb * G], st.sampled[:nb * G], st.sampled_lp[:nb * G])
+        ops.lookup_accept(st.sampled[:nb * G], st.sampled_lp[:nb * G], st.inp[:nb], st.n_draft[:nb],
+                          self.out_tokens[:nb], self.out_logp[:nb], self.hist[:nb], self.active[:nb],
+                          self.kv_len[:nb], self.pos[:nb], self.attn_len[:nb], self.kv_start[:nb],
+                          self.gen_len[:nb], self.step, self.rng_offset, st.counters, eos_ids)
+        self._draft(params, pad_id)
+
+    def _draft(self, params: SamplingParams, pad_id: int):
+        nb, st = self._nb, self._lk
+        ops.lookup_draft(self.hist[:nb], self.kv_len[:nb], self.kv_start[:nb], self.active[:nb],
+                         params.lookup_ngram, pad_id, st.inp[:nb], st.n_draft[:nb], st.row_active[:nb * st.G])
 
     def _emit(self, h, params: SamplingParams, eos_ids, pad_id, r0: int = 0):
         """Sample from the hidden states of rows [r0, r0 + len(h)) and run the bookkeeping for them
@@ -266,7 +321,10 @@ class Generator:
         T = params.max_new_tokens
         if params.max_length is not None:
             T = max(1, min(T, params.max_length - S))
-        assert S + T <= self.max_seq, f"prompt {S} + new {T} exceeds cache {self.max_seq}"
+        self._check_lookup(params)
+        K = params.lookup_tokens
+        # the last verify step may append K rows past the last emitted token
+        assert S + T + K <= self.max_seq, f"prompt {S} + new {T} (+ {K} draft) exceeds cache {self.max_seq}"
         t0 = time.perf_counter()
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if dev.type == "cuda" else None
         if ev:
@@ -317,9 +375,18 @@ class Generator:
             packed = packed_index(start.numpy(), np.full(B, S), S, dev)
         h_last = self.model.prefill(ids, self.kv_start[:B], sub, packed=packed) if packed is not None else \
             self.model.prefill(ids, self.kv_start[:B], sub)
-        if hasattr(self.model, "refresh_decode_weights"):
-            self.model.refresh_decode_weights(self._bucket(B))  # folded / tile-ordered / fp8 images of graph replays
+        K = params.lookup_tokens
         self._nb = self._bucket(B)
+        if K > 0 and dev.type == "cuda":
+            layers = getattr(self.model, "layers", None)
+            fp8 = bool(layers) and getattr(layers[0], "fp8_enabled", False)
+            max_b = getattr(self.model, "fused_decode_max_batch_fp8" if fp8 else "fused_decode_max_batch", None)
+            if max_b is not None and self._nb * (K + 1) > max_b:
+                raise ValueError(f"prompt-lookup decoding: {self._nb} rows x {K + 1} positions exceed the fused "
+                                 f"decode layer's limit of {max_b} rows")
+        if hasattr(self.model, "refresh_decode_weights"):
+            # folded / tile-ordered / fp8 images of graph replays; a verify step runs rows * (K + 1) rows
+            self.model.refresh_decode_weights(self._nb * (K + 1))
         h = torch.zeros(self._nb, cfg.hidden_size, dtype=h_last.dtype, device=dev)
         h[:B] = h_last
         # the first sampled token is not in the cache yet: the bookkeeping kernel advances kv_len
@@ -329,6 +396,16 @@ class Generator:
         if ev:
             ev[1].record()
         steps = T - 1
+        self._lk = None
+        if K > 0:
+            st = self._lk = self._lookup_buffers(K)
+            st.counters.zero_()  # reported (as zeros) even when no verify step runs (T == 1)
+        if K > 0 and steps > 0:
+            # history = the left-padded prompt, then the first sampled token at slot S (= kv_len, where
+            # the first verify step appends it); the first draft is made outside the captured step
+            self.hist[:B, :S] = ids
+            self.hist[:self._nb, S] = self.tok_in[:self._nb]
+            self._draft(params, pad_id)
         if steps > 0:
             self._ensure_graph(params, eos, eos_list, pad_id, T)
         loop = _DecodeLoop(self, steps, params, eos, pad_id, early_stop)
@@ -343,20 +420,30 @@ class Generator:
         """The captured decode step for (sampling parameters, output width, row bucket)."""
         key = (T, params.inv_temp, params.top_k, params.top_p, params.greedy, params.seed, tuple(eos_list), pad_id,
                self._nb)
+        step = self._step
+        if self._lk is not None:
+            # a verify step is its own graph per (K, n-gram length); plain keys are unchanged
+            key = key + ("lookup", params.lookup_tokens, params.lookup_ngram)
+            step = self._step_verify
         if self.use_graph and self.runner.needs(key):
             # the EOS tensor is created per call: the runner keeps the captured one alive
-            self.runner.capture(lambda: self._step(params, eos, pad_id), key, keep=(eos,), restore=self._state())
+            self.runner.capture(lambda: step(params, eos, pad_id), key, keep=(eos,), restore=self._state())
 
     def _replay(self, params, eos, pad_id):
         if self.use_graph:
             self.runner.replay()
+        elif self._lk is not None:
+            self._step_verify(params, eos, pad_id)
         else:
             self._step(params, eos, pad_id)
 
     def _state(self):
-        return [self.tok_in, self.kv_len, self.pos, self.attn_len, self.active, self.gen_len, self.step,
-                self.rng_offset, self.sampled, self.sampled_lp, self.values, self.out_tokens, self.out_logp,
-                self.out_values]
+        st = [self.tok_in, self.kv_len, self.pos, self.attn_len, self.active, self.gen_len, self.step,
+              self.rng_offset, self.sampled, self.sampled_lp, self.values, self.out_tokens, self.out_logp,
+              self.out_values]
+        if self._lk is not None:
+            st += [self.hist] + self._lk.tensors()
+        return st
 
 
 class _DecodeLoop:
@@ -438,6 +525,7 @@ class _Pending:
     def __init__(self, gen: "Generator", B, ids, start, t0, ev, loop: Optional[_DecodeLoop] = None):
         self.gen, self.B, self.ids, self.start, self.t0, self.ev = gen, B, ids, start, t0, ev
         self.loop = loop
+        self.lk = gen._lk  # this generation's lookup buffers (None: plain decoding)
         self._recorded = False
 
     @torch.no_grad()
@@ -468,9 +556,29 @@ class _Pending:
             tim["decode_s"] = self.ev[1].elapsed_time(self.ev[2]) / 1e3
         if self.loop is not None:
             tim["decode_steps"] = self.loop.done
+        if self.lk is not None:
+            # summed over rows, read once here (no per-step host sync)
+            c = self.lk.counters.tolist()
+            tim["lookup_steps"], tim["lookup_drafted"], tim["lookup_accepted"] = int(c[0]), int(c[1]), int(c[2])
         return GenerationOutput(g.out_tokens[:B].clone(), g.gen_len[:B].clone().long(), g.out_logp[:B].clone(),
                                 g.out_values[:B].clone() if g.value_head is not None else None, self.ids,
                                 self.start.to(g.device).long(), tim)
+
+
+class _LookupState:
+    """Static buffers of the verify step for one K (G = K + 1 positions per row)."""
+
+    def __init__(self, B: int, G: int, device):
+        self.G = G
+        self.inp = torch.zeros(B, G, dtype=torch.long, device=device)          # last emitted token | draft
+        self.n_draft = torch.zeros(B, dtype=torch.int32, device=device)
+        self.row_active = torch.zeros(B * G, dtype=torch.uint8, device=device)  # the sampler's row mask
+        self.sampled = torch.zeros(B * G, dtype=torch.long, device=device)
+        self.sampled_lp = torch.zeros(B * G, dtype=torch.float32, device=device)
+        self.counters = torch.zeros(3, dtype=torch.long, device=device)         # row-steps, drafted, accepted
+
+    def tensors(self):
+        return [self.inp, self.n_draft, self.row_active, self.sampled, self.sampled_lp, self.counters]
 
 
 class _SubCache:
@@ -543,8 +651,11 @@ class ContinuousBatcher:
     rows that finished (a host read of the per-row flags once per call)."""
 
     def __init__(self, gen: Generator, params: SamplingParams, pad_id: int = 0, eos_ids: Sequence[int] = ()):
+        if params.lookup_tokens > 0:
+            raise NotImplementedError("prompt-lookup decoding is not supported with continuous batching")
         self.gen, self.params, self.pad_id = gen, params, pad_id
         g = gen
+        g._lk = None
         dev, MB, T = g.device, g.max_batch, params.max_new_tokens
         self.T = T
         self.eos_list = list(eos_ids) or [g.cfg.eos_token_id]

@@ -424,6 +424,44 @@ class CausalLM(nn.Module):
             x, residual = layer.mlp(o, residual, defer)
         return self.final_norm(x, residual)
 
+    @torch.no_grad()
+    def decode_verify(self, tokens, pos0, slot0, attn_len0, kv_start, cache, workspace=None) -> torch.Tensor:
+        """One verify step (prompt-lookup speculative decoding): tokens [B, G] are G consecutive
+        positions of every sequence, position j at rotary position pos0 + j, written to cache slot
+        slot0 + j and attending over attn_len0 + j keys (``ops.verify_step_attention``). Everything
+        but attention is row-local and runs the decode step's layer on B * G rows. Returns the final
+        hidden [B * G, H] (row b * G + j). ``workspace``: the decode step's (its key partitioning is
+        followed at head_dim 64; nothing is written to it)."""
+        cfg = self.cfg
+        if cfg.arch == "opt":
+            raise NotImplementedError("decode_verify: learned-position (opt) models are not supported")
+        if getattr(cache, "fp8", False):
+            raise NotImplementedError("decode_verify: fp8 K/V cache is not supported")
+        B, G = tokens.shape
+        fp8 = bool(self.layers) and self.layers[0].fp8_enabled
+        max_b = self.fused_decode_max_batch_fp8 if fp8 else self.fused_decode_max_batch
+        if tokens.is_cuda and B * G > max_b:
+            raise ValueError(f"decode_verify: {B} rows x {G} positions exceed the fused decode layer's "
+                             f"limit of {max_b} rows")
+        cos, sin = self.rope(tokens.device)
+        x = self.embed_tokens(tokens.reshape(-1), None)
+
+        def attend_layer(qkv, li):
+            return ops.verify_step_attention(qkv, cache.k[li], cache.v[li], slot0, attn_len0, cfg.num_heads, G,
+                                             pos0, cos, sin, kv_start, cfg.sliding_window, workspace=workspace)
+
+        if self.fused_decode and x.is_cuda and not torch.is_grad_enabled():
+            h = x
+            for li, layer in enumerate(self.layers):
+                h = layer.decode_fused(h, lambda qkv, li=li: attend_layer(qkv, li))
+            y, _ = ops.rms_norm(h, self.norm_w, cfg.norm_eps)
+            return y
+        residual = None
+        for li, layer in enumerate(self.layers):
+            qkv, residual = layer.attn_in(x, residual, False)
+            x, residual = layer.mlp(attend_layer(qkv, li), residual, False)
+        return self.final_norm(x, residual)
+
     # ------------------------------------------------------------------ LoRA
     def add_lora(self, r: int = 16, alpha: float = 32.0, targets=None, dropout: float = 0.0, seed: int = 0):
         """Attach PEFT-style LoRA adapters (A kaiming-uniform, B zero) to the target projections."""

@@ -10,9 +10,10 @@ from .norm import layer_norm, rms_norm  # noqa: F401
 from .attention import (  # noqa: F401
     attention, decode_attention, decode_step_attention, decode_workspace, flash_attention_packed, gather_rows, packed_inverse, scatter_rows,
     flash_attention_qkv, rope_qkv, rope_qkv_, FP8_KV_D, kv_dequantize, kv_quantize_rows, kv_store_fp8,
+    verify_step_attention,
 )
 from .misc import (embedding, gae, ivf_scan, ppo_advantages, pool_normalize, ppo_loss, row_dot, sample, segment_mean,  # noqa: F401
-                   swiglu, token_logprobs, topk)
+                   swiglu, token_logprobs, topk, lookup_accept, lookup_draft)
 from .optim import FlatParams, FusedAdamW, MixedFlatParams, flat_params  # noqa: F401
 from .fp8 import Fp8Cache, dequantize_fp8, gemm_fp8, quantize_fp8  # noqa: F401
 from . import reference  # noqa: F401

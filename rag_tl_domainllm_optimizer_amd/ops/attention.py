@@ -376,6 +376,45 @@ def decode_step_attention(qkv, k_cache, v_cache, slot, attn_len, Hq, pos=None, c
     return out
 
 
+def verify_step_attention(qkv, k_cache, v_cache, slot0, attn_len0, Hq, G, pos0=None, cos=None, sin=None,
+                          kv_start=None, window=0, scale=None, out=None, sign: float = 1.0, workspace=None):
+    """One verify step of a layer (prompt-lookup speculative decoding), fused: rows ``b*G + j`` of the
+    unrotated ``qkv`` [B*G, (Hq + 2 Hkv) D] are G consecutive positions of sequence b. Position j is
+    rotated at ``pos0[b] + j``, its K / V row appended at cache slot ``slot0[b] + j``, and it attends
+    to the keys ``[max(kv_start, len_j - window), len_j)``, ``len_j = attn_len0[b] + j`` — exactly G
+    successive ``decode_step_attention`` calls, with the cache row streamed once. Contract:
+    ``slot0 == attn_len0 - 1`` and ``slot0 + G <= Smax``. bf16 caches [B, Hkv, Smax, D] -> [B*G, Hq*D].
+    head_dim 128: the MFMA kernel (cache row read once). head_dim 64 (where the decode step itself
+    runs its VALU kernel): that kernel's arithmetic per position over the key partitions of
+    ``workspace`` (the decode step's; default: the one ``decode_workspace`` would size) — outputs are
+    bitwise those of the successive decode steps. Nothing is written to the workspace."""
+    B, Hkv, Smax, D = k_cache.shape
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if k_cache.dtype == torch.uint8:
+        raise NotImplementedError("verify_step_attention: fp8 K/V cache is not supported")
+    if not 1 <= G <= 8:
+        raise ValueError(f"verify_step_attention: G = {G} positions per row, supported 1..8")
+    if not on_gpu(qkv):
+        pos = None
+        if cos is not None:
+            pos = (pos0.long()[:, None] + torch.arange(G, device=qkv.device)[None]).reshape(-1).to(torch.int32)
+        q = rope_qkv_(qkv.clone(), pos, cos, sin, Hq, Hkv, D, S=G, k_cache=k_cache, v_cache=v_cache,
+                      slot_base=slot0, sign=sign)
+        o = ref.verify_attention(q, k_cache, v_cache, attn_len0, Hq, G, kv_start, window, scale)
+        if out is not None:
+            out.copy_(o)
+            return out
+        return o
+    if D not in (64, 128) or Hq // Hkv not in (1, 2, 4, 8) or Hq % Hkv:
+        raise NotImplementedError(f"verify_step_attention: head_dim {D}, {Hq} / {Hkv} heads")
+    if out is None:
+        out = torch.empty(B * G, Hq * D, dtype=qkv.dtype, device=qkv.device)
+    PS = workspace[1] if workspace is not None and len(workspace) > 1 else decode_partition(B * Hkv, D, Smax)
+    native().attn_verify(qkv, k_cache, v_cache, slot0, attn_len0, kv_start, pos0, cos, sin, sign, window, scale, Hq, G,
+                         PS, out)
+    return out
+
+
 def decode_attention(q, k_cache, v_cache, kv_len, Hq, kv_start=None, window=0, scale=None, workspace=None, out=None):
     """One query token per sequence against a KV cache [B, Hkv, Smax, D] -> [B, Hq*D]."""
     B, Hkv, Smax, D = k_cache.shape

@@ -150,6 +150,33 @@ def sample(logits, inv_temp=1.0, top_k=0, top_p=1.0, greedy=False, seed=0, offse
     return out_tok, out_logp
 
 
+# ------------------------------------------------- prompt-lookup speculative decoding bookkeeping
+def lookup_accept(sampled, logp, inp, n_draft, out_tokens, out_logp, hist, active, kv_len, pos, attn_len, kv_start,
+                  gen_len, step, rng_offset, counters, eos_ids):
+    """Bookkeeping of a verify step, in place (``lookup_accept_kernel``): per active row accept the
+    longest draft prefix ``inp[b, 1:]`` the sampler reproduced in ``sampled`` [B, G], emit
+    ``sampled[b, :a + 1]`` (cut after the first EOS and at the output width) with its log-probs at
+    the row's output position and into ``hist`` [B, Smax], advance the row's lengths.
+    ``counters`` int64 [3]: row-steps, drafted tokens, accepted-and-emitted tokens."""
+    args = (sampled, logp, inp, n_draft, out_tokens, out_logp, hist, active, kv_len, pos, attn_len, kv_start,
+            gen_len, step, rng_offset, counters, eos_ids)
+    if on_gpu(inp):
+        native().lookup_accept(*args)
+    else:
+        ref.lookup_accept(*args)
+
+
+def lookup_draft(hist, kv_len, kv_start, active, ngram, pad_id, inp, n_draft, row_active):
+    """The next verify step's inputs, in place (``lookup_draft_kernel``): ``inp[b, 0]`` = the last
+    emitted token ``hist[b, kv_len[b]]``, ``inp[b, 1:]`` = the tokens that followed the latest earlier
+    occurrence of the row's last n-gram (n = ``ngram`` .. 1, starts in ``[kv_start, end - n)``),
+    ``n_draft[b]`` of them real and the rest pad; ``row_active`` [B*G] = the row's flag per position."""
+    if on_gpu(inp):
+        native().lookup_draft(hist, kv_len, kv_start, active, ngram, pad_id, inp, n_draft, row_active)
+    else:
+        ref.lookup_draft(hist, kv_len, kv_start, active, ngram, pad_id, inp, n_draft, row_active)
+
+
 # ------------------------------------------------------------------------------- retrieval
 def pool_normalize(x: torch.Tensor, lengths=None, normalize: bool = True) -> torch.Tensor:
     """Masked mean over tokens + L2 normalisation: [B, S, H] -> [B, H] fp32."""

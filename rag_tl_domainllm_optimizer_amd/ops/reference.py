@@ -318,3 +318,87 @@ def ppo_advantages(old_logp, ref_logp, values, scores, resp_len, kl_coef, gamma,
         var = (((adv - mean) ** 2) * m).sum() / n
         adv = (adv - mean) * torch.rsqrt(var + eps) * m
     return adv, ret, rewards, kl.sum(-1)
+
+
+# ------------------------------------------------------------- prompt-lookup speculative decoding
+def verify_attention(q, kc, vc, attn_len0, Hq, G, kv_start=None, window=0, scale=None):
+    """Attention of a verify step. q [B*G, >=Hq*D] (rotated; rows b*G+j = G consecutive positions of
+    sequence b) against caches [B, Hkv, Smax, D] that already hold the G new rows: position j sees
+    the keys [max(kv_start, len_j - window), len_j), len_j = attn_len0 + j. Returns o [B*G, Hq*D]."""
+    B, Hkv, Smax, D = kc.shape
+    out = []
+    for j in range(G):
+        out.append(decode_attention(q[j::G], kc, vc, attn_len0 + j, Hq, kv_start, window, scale))
+    return torch.stack(out, 1).reshape(B * G, Hq * D)
+
+
+def lookup_accept(sampled, logp, inp, n_draft, out_tokens, out_logp, hist, active, kv_len, pos, attn_len, kv_start,
+                  gen_len, step, rng_offset, counters, eos_ids):
+    """Twin of lookup_accept_kernel (in place). sampled / logp / inp [B, G]; see csrc/kernels/rl.hip."""
+    B, G = inp.shape
+    T, Smax = out_tokens.shape[1], hist.shape[1]
+    eos = set(int(e) for e in eos_ids.tolist())
+    sm, lp = sampled.reshape(B, G), logp.reshape(B, G)
+    for b in range(B):
+        gl, kl = int(gen_len[b]), int(kv_len[b])
+        if int(active[b]) != 0 and gl < T:
+            nd = min(max(int(n_draft[b]), 0), G - 1)
+            a = 0
+            while a < nd and int(sm[b, a]) == int(inp[b, a + 1]):
+                a += 1
+            e, fin = 0, False
+            for i in range(a + 1):
+                t = int(sm[b, i])
+                out_tokens[b, gl + i] = t
+                out_logp[b, gl + i] = lp[b, i]
+                if kl + 1 + i < Smax:
+                    hist[b, kl + 1 + i] = t
+                e = i + 1
+                fin = gl + e >= T or t in eos
+                if fin:
+                    break
+            gen_len[b] = gl + e
+            kv_len[b] = kl + e
+            if fin:
+                active[b] = 0
+            counters[0] += 1
+            counters[1] += nd
+            counters[2] += e - 1
+        attn_len[b] = int(kv_len[b]) + 1
+        pos[b] = int(kv_len[b]) - int(kv_start[b])
+    step += 1
+    rng_offset += 1
+
+
+def lookup_draft(hist, kv_len, kv_start, active, ngram, pad_id, inp, n_draft, row_active):
+    """Twin of lookup_draft_kernel (in place): inp [B, G] = last emitted token | draft, n_draft [B],
+    row_active [B*G]."""
+    B, G = inp.shape
+    Smax = hist.shape[1]
+    ra = row_active.reshape(-1)
+    for b in range(B):
+        act = int(active[b]) != 0
+        ra[b * G:(b + 1) * G] = 1 if act else 0
+        kl = int(kv_len[b])
+        if not act or kl < 0 or kl >= Smax:
+            inp[b].fill_(pad_id)
+            n_draft[b] = 0
+            continue
+        h = hist[b].tolist()
+        end, ks = kl + 1, max(int(kv_start[b]), 0)
+        best, bn = -1, 0
+        for n in range(int(ngram), 0, -1):
+            bn = n
+            tail = h[end - n:end] if end - n >= 0 else None
+            for i in range(end - n - 1, ks - 1, -1):  # latest start first
+                if h[i:i + n] == tail:
+                    best = i
+                    break
+            if best >= 0:
+                break
+        cont = best + bn
+        avail = min(G - 1, end - cont) if best >= 0 else 0
+        inp[b, 0] = h[kl]
+        for j in range(1, G):
+            inp[b, j] = h[cont + j - 1] if j - 1 < avail else pad_id
+        n_draft[b] = avail

@@ -36,7 +36,9 @@ class RagPipeline:
         self.top_k = top_k
         self.sampling = sampling or SamplingParams(max_new_tokens=128)
         self.max_prompt_tokens = max_prompt_tokens
-        self.gen = Generator(model, max_batch, max_prompt_tokens + self.sampling.max_new_tokens + 8,
+        # prompt-lookup decoding: the last verify step may append lookup_tokens rows past the answer
+        self.gen = Generator(model, max_batch,
+                             max_prompt_tokens + self.sampling.max_new_tokens + 8 + self.sampling.lookup_tokens,
                              use_graph=use_graph)
         self.max_batch = max_batch
 

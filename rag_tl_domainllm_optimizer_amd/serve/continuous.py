@@ -28,6 +28,8 @@ from ..rag.prompt import extract_answer
 
 class ContinuousEngine:
     def __init__(self, pipeline, chunk: int = 4):
+        if pipeline.sampling.lookup_tokens > 0:
+            raise NotImplementedError("prompt-lookup decoding is not supported with continuous batching")
         self.pipeline = pipeline
         self.chunk = max(1, chunk)
         self._q: "queue.Queue" = queue.Queue()
