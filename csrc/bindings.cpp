@@ -898,6 +898,49 @@ static KvScales check_cache(const Tensor& kc, const Tensor& vc, const optional<T
   return r;
 }
 
+// What the decode-step family (attn_decode_fused, attn_decode_fused_slabs, attn_verify) checks
+// alike: the cache (check_cache) and its layout, Hq a multiple of Hkv, G rows per sequence in
+// qkv (null: q | k | v come as split-K slabs, checked by the caller) and out with one slot /
+// attn_len entry per sequence, the row widths, the rotary tables with pos, and kv_start's dtype.
+struct DecodeStep {
+  int64_t B, Hkv, Smax, D;
+  KvScales sc;
+  const int* pos = nullptr;  // all three null: no rotary
+  const float* cos = nullptr;
+  const float* sin = nullptr;
+};
+static DecodeStep check_decode_step(const Tensor* qkv_rows, const Tensor& kc, const Tensor& vc,
+                                    const optional<Tensor>& ksc, const optional<Tensor>& vsc, const Tensor& slot,
+                                    const Tensor& attn_len, const optional<Tensor>& kv_start,
+                                    const optional<Tensor>& pos, const optional<Tensor>& cos,
+                                    const optional<Tensor>& sin, int64_t Hq, int64_t G, const Tensor& out,
+                                    const char* who) {
+  DecodeStep r;
+  r.sc = check_cache(kc, vc, ksc, vsc, who);
+  CHECK_I32(slot); CHECK_I32(attn_len); CHECK_BF16(out); CHECK_ROWS(out);
+  TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.is_contiguous() && vc.sizes() == kc.sizes(), who,
+              ": cache layout");
+  r.B = kc.size(0); r.Hkv = kc.size(1); r.Smax = kc.size(2); r.D = kc.size(3);
+  TORCH_CHECK(r.Hkv > 0 && Hq % r.Hkv == 0, who, ": Hq must be a multiple of Hkv");
+  TORCH_CHECK(out.size(0) == r.B * G && slot.numel() == r.B && attn_len.numel() == r.B, who, ": batch");
+  TORCH_CHECK(out.size(1) >= Hq * r.D, who, ": widths");
+  if (qkv_rows) {
+    const Tensor& qkv = *qkv_rows;
+    CHECK_CUDA(qkv); CHECK_BF16(qkv); CHECK_ROWS(qkv);
+    TORCH_CHECK(qkv.size(0) == r.B * G, who, ": batch");
+    TORCH_CHECK(qkv.size(1) >= (Hq + 2 * r.Hkv) * r.D, who, ": widths");
+  }
+  if (cos.has_value() && cos->defined()) {
+    TORCH_CHECK(sin.has_value() && sin->defined() && pos.has_value() && pos->defined(), who,
+                ": rotary needs sin and pos");
+    CHECK_F32(*cos); CHECK_F32(*sin); CHECK_I32(*pos);
+    TORCH_CHECK(cos->size(-1) == r.D / 2 && cos->is_contiguous() && sin->is_contiguous(), who, ": tables");
+    r.pos = pos->data_ptr<int>(); r.cos = cos->data_ptr<float>(); r.sin = sin->data_ptr<float>();
+  }
+  if (kv_start.has_value() && kv_start->defined()) CHECK_I32(*kv_start);
+  return r;
+}
+
 // Prompt K / V of the rotated qkv rows [B * S] -> fp8 cache slots [0, S) with per-slot scales.
 void kv_store_fp8(const Tensor& qkv, Tensor kc, Tensor vc, Tensor ksc, Tensor vsc, int64_t B, int64_t S, int64_t Hq) {
   CHECK_CUDA(qkv); CHECK_BF16(qkv); CHECK_ROWS(qkv); CHECK_F32(ksc); CHECK_F32(vsc);
@@ -918,34 +961,18 @@ void attn_decode_fused(const Tensor& qkv, Tensor kc, Tensor vc, const Tensor& sl
                        const optional<Tensor>& sin, double sign, int64_t window, double scale, int64_t Hq, Tensor part,
                        Tensor tickets, int64_t PS, Tensor out, const optional<Tensor>& ksc,
                        const optional<Tensor>& vsc, const optional<Tensor>& stamps) {
-  const KvScales sc = check_cache(kc, vc, ksc, vsc, "attn_decode_fused");
-  CHECK_CUDA(qkv); CHECK_BF16(qkv); CHECK_ROWS(qkv); CHECK_I32(slot);
-  CHECK_I32(attn_len); CHECK_F32(part); CHECK_I32(tickets); CHECK_BF16(out); CHECK_ROWS(out);
-  TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.is_contiguous() && vc.sizes() == kc.sizes(),
-              "attn_decode_fused: cache layout");
-  const int64_t B = kc.size(0), Hkv = kc.size(1), Smax = kc.size(2), D = kc.size(3);
-  const int64_t NP = (Smax + PS - 1) / PS, G = Hq / Hkv;
-  TORCH_CHECK(G * Hkv == Hq, "attn_decode_fused: Hq must be a multiple of Hkv");
-  TORCH_CHECK(qkv.size(0) == B && out.size(0) == B && slot.numel() == B && attn_len.numel() == B,
-              "attn_decode_fused: batch");
-  TORCH_CHECK(qkv.size(1) >= (Hq + 2 * Hkv) * D && out.size(1) >= Hq * D, "attn_decode_fused: widths");
-  TORCH_CHECK(part.numel() >= B * Hkv * NP * G * (D + 2), "attn_decode_fused: partial workspace too small");
-  TORCH_CHECK(tickets.numel() >= B * Hkv, "attn_decode_fused: ticket workspace too small");
-  const bool rot = cos.has_value() && cos->defined();
-  if (rot) {
-    CHECK_F32(*cos); CHECK_F32(*sin);
-    TORCH_CHECK(pos.has_value() && pos->defined(), "attn_decode_fused: rotary needs pos");
-    CHECK_I32(*pos);
-    TORCH_CHECK(cos->size(-1) == D / 2 && cos->is_contiguous() && sin->is_contiguous(), "attn_decode_fused: tables");
-  }
-  if (kv_start.has_value() && kv_start->defined()) CHECK_I32(*kv_start);
-  check_rc(rt_attn_decode_fused(qkv.data_ptr(), qkv.stride(0), kc.data_ptr(), vc.data_ptr(), (int)Smax,
-                                slot.data_ptr<int>(), attn_len.data_ptr<int>(), (const int*)opt_ptr(kv_start),
-                                rot ? pos->data_ptr<int>() : nullptr, rot ? cos->data_ptr<float>() : nullptr,
-                                rot ? sin->data_ptr<float>() : nullptr, (float)sign, (int)window,
-                                part.data_ptr<float>(), (unsigned*)tickets.data_ptr<int>(), (int)NP, (int)PS,
-                                out.data_ptr(), out.stride(0), (int)B, (int)Hq, (int)Hkv, (int)D, (float)scale,
-                                nullptr, 0, sc.k, sc.v, sc.smaxp,
+  const DecodeStep c = check_decode_step(&qkv, kc, vc, ksc, vsc, slot, attn_len, kv_start, pos, cos, sin, Hq, 1, out,
+                                         "attn_decode_fused");
+  CHECK_F32(part); CHECK_I32(tickets);
+  const int64_t NP = (c.Smax + PS - 1) / PS, G = Hq / c.Hkv;
+  TORCH_CHECK(part.numel() >= c.B * c.Hkv * NP * G * (c.D + 2), "attn_decode_fused: partial workspace too small");
+  TORCH_CHECK(tickets.numel() >= c.B * c.Hkv, "attn_decode_fused: ticket workspace too small");
+  check_rc(rt_attn_decode_fused(qkv.data_ptr(), qkv.stride(0), kc.data_ptr(), vc.data_ptr(), (int)c.Smax,
+                                slot.data_ptr<int>(), attn_len.data_ptr<int>(), (const int*)opt_ptr(kv_start), c.pos,
+                                c.cos, c.sin, (float)sign, (int)window, part.data_ptr<float>(),
+                                (unsigned*)tickets.data_ptr<int>(), (int)NP, (int)PS, out.data_ptr(), out.stride(0),
+                                (int)c.B, (int)Hq, (int)c.Hkv, (int)c.D, (float)scale, nullptr, 0, c.sc.k, c.sc.v,
+                                c.sc.smaxp,
                                 stamps.has_value() && stamps->defined() ? (long long*)stamps->data_ptr() : nullptr,
                                 cur_stream()),
            "attn_decode_fused");
@@ -959,35 +986,21 @@ bool attn_decode_fused_slabs(const Tensor& slabs, int64_t nsplit, Tensor kc, Ten
                              const optional<Tensor>& cos, const optional<Tensor>& sin, double sign, int64_t window,
                              double scale, int64_t Hq, Tensor part, Tensor tickets, int64_t PS, Tensor out,
                              const optional<Tensor>& ksc, const optional<Tensor>& vsc) {
-  const KvScales sc = check_cache(kc, vc, ksc, vsc, "attn_decode_fused_slabs");
-  CHECK_CUDA(slabs); CHECK_F32(slabs); CHECK_I32(slot); CHECK_I32(attn_len);
-  CHECK_F32(part); CHECK_I32(tickets); CHECK_BF16(out); CHECK_ROWS(out);
-  TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.is_contiguous() && vc.sizes() == kc.sizes(),
-              "attn_decode_fused_slabs: cache layout");
-  const int64_t B = kc.size(0), Hkv = kc.size(1), Smax = kc.size(2), D = kc.size(3);
-  const int64_t NP = (Smax + PS - 1) / PS, G = Hq / Hkv;
-  TORCH_CHECK(G * Hkv == Hq, "attn_decode_fused_slabs: Hq must be a multiple of Hkv");
-  if (!rt_attn_decode_mfma_ok((int)B, (int)Hq, (int)Hkv, (int)D, (int)NP)) return false;  // caller reduces first
-  const int64_t W = (Hq + 2 * Hkv) * D;
-  TORCH_CHECK(slabs.is_contiguous() && slabs.numel() >= nsplit * B * W && nsplit >= 1, "attn_decode_fused_slabs: slabs");
-  TORCH_CHECK(out.size(0) == B && slot.numel() == B && attn_len.numel() == B && out.size(1) >= Hq * D,
-              "attn_decode_fused_slabs: batch");
-  TORCH_CHECK(tickets.numel() >= B * Hkv && part.numel() >= B * Hkv * NP * G * (D + 2), "attn_decode_fused_slabs: ws");
-  const bool rot = cos.has_value() && cos->defined();
-  if (rot) {
-    CHECK_F32(*cos); CHECK_F32(*sin);
-    TORCH_CHECK(pos.has_value() && pos->defined(), "attn_decode_fused_slabs: rotary needs pos");
-    CHECK_I32(*pos);
-    TORCH_CHECK(cos->size(-1) == D / 2 && cos->is_contiguous() && sin->is_contiguous(), "attn_decode_fused_slabs: tables");
-  }
-  if (kv_start.has_value() && kv_start->defined()) CHECK_I32(*kv_start);
-  check_rc(rt_attn_decode_fused(slabs.data_ptr(), W, kc.data_ptr(), vc.data_ptr(), (int)Smax, slot.data_ptr<int>(),
-                                attn_len.data_ptr<int>(), (const int*)opt_ptr(kv_start),
-                                rot ? pos->data_ptr<int>() : nullptr, rot ? cos->data_ptr<float>() : nullptr,
-                                rot ? sin->data_ptr<float>() : nullptr, (float)sign, (int)window,
-                                part.data_ptr<float>(), (unsigned*)tickets.data_ptr<int>(), (int)NP, (int)PS,
-                                out.data_ptr(), out.stride(0), (int)B, (int)Hq, (int)Hkv, (int)D, (float)scale,
-                                slabs.data_ptr<float>(), (int)nsplit, sc.k, sc.v, sc.smaxp, nullptr, cur_stream()),
+  const DecodeStep c = check_decode_step(nullptr, kc, vc, ksc, vsc, slot, attn_len, kv_start, pos, cos, sin, Hq, 1, out,
+                                         "attn_decode_fused_slabs");
+  CHECK_CUDA(slabs); CHECK_F32(slabs); CHECK_F32(part); CHECK_I32(tickets);
+  const int64_t NP = (c.Smax + PS - 1) / PS, G = Hq / c.Hkv;
+  if (!rt_attn_decode_mfma_ok((int)c.B, (int)Hq, (int)c.Hkv, (int)c.D, (int)NP)) return false;  // caller reduces first
+  const int64_t W = (Hq + 2 * c.Hkv) * c.D;
+  TORCH_CHECK(slabs.is_contiguous() && slabs.numel() >= nsplit * c.B * W && nsplit >= 1, "attn_decode_fused_slabs: slabs");
+  TORCH_CHECK(tickets.numel() >= c.B * c.Hkv && part.numel() >= c.B * c.Hkv * NP * G * (c.D + 2),
+              "attn_decode_fused_slabs: ws");
+  check_rc(rt_attn_decode_fused(slabs.data_ptr(), W, kc.data_ptr(), vc.data_ptr(), (int)c.Smax, slot.data_ptr<int>(),
+                                attn_len.data_ptr<int>(), (const int*)opt_ptr(kv_start), c.pos, c.cos, c.sin,
+                                (float)sign, (int)window, part.data_ptr<float>(), (unsigned*)tickets.data_ptr<int>(),
+                                (int)NP, (int)PS, out.data_ptr(), out.stride(0), (int)c.B, (int)Hq, (int)c.Hkv,
+                                (int)c.D, (float)scale, slabs.data_ptr<float>(), (int)nsplit, c.sc.k, c.sc.v,
+                                c.sc.smaxp, nullptr, cur_stream()),
            "attn_decode_fused_slabs");
   return true;
 }
@@ -1328,33 +1341,16 @@ void attn_verify(const Tensor& qkv, Tensor kc, Tensor vc, const Tensor& slot0, c
                  const optional<Tensor>& kv_start, const optional<Tensor>& pos0, const optional<Tensor>& cos,
                  const optional<Tensor>& sin, double sign, int64_t window, double scale, int64_t Hq, int64_t G,
                  int64_t PS, Tensor out) {
-  CHECK_CUDA(qkv); CHECK_BF16(qkv); CHECK_ROWS(qkv); CHECK_ALIGN16(qkv); CHECK_I32(slot0); CHECK_I32(attn_len0);
-  CHECK_BF16(out); CHECK_ROWS(out); CHECK_ALIGN16(out); CHECK_BF16(kc); CHECK_BF16(vc);
-  TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.is_contiguous() && vc.sizes() == kc.sizes(),
-              "attn_verify: cache layout");
-  const int64_t B = kc.size(0), Hkv = kc.size(1), Smax = kc.size(2), D = kc.size(3);
-  TORCH_CHECK(G >= 1 && G <= 8 && Hkv > 0 && Hq % Hkv == 0, "attn_verify: 1 <= G <= 8, Hq a multiple of Hkv");
-  TORCH_CHECK(qkv.size(0) == B * G && out.size(0) == B * G && slot0.numel() == B && attn_len0.numel() == B,
-              "attn_verify: batch");
-  TORCH_CHECK(qkv.size(1) >= (Hq + 2 * Hkv) * D && out.size(1) >= Hq * D, "attn_verify: widths");
-  const bool rot = cos.has_value() && cos->defined();
-  if (rot) {
-    CHECK_F32(*cos); CHECK_F32(*sin);
-    TORCH_CHECK(pos0.has_value() && pos0->defined(), "attn_verify: rotary needs pos0");
-    CHECK_I32(*pos0);
-    TORCH_CHECK(pos0->numel() == B && cos->size(-1) == D / 2 && cos->is_contiguous() && sin->is_contiguous(),
-                "attn_verify: tables");
-  }
-  if (kv_start.has_value() && kv_start->defined()) {
-    CHECK_I32(*kv_start);
-    TORCH_CHECK(kv_start->numel() == B, "attn_verify: kv_start");
-  }
-  check_rc(rt_attn_verify(qkv.data_ptr(), qkv.stride(0), kc.data_ptr(), vc.data_ptr(), (int)Smax,
-                          slot0.data_ptr<int>(), attn_len0.data_ptr<int>(), (const int*)opt_ptr(kv_start),
-                          rot ? pos0->data_ptr<int>() : nullptr, rot ? cos->data_ptr<float>() : nullptr,
-                          rot ? sin->data_ptr<float>() : nullptr, (float)sign, (int)window, out.data_ptr(),
-                          out.stride(0), (int)B, (int)G, (int)Hq, (int)Hkv, (int)D, (float)scale, (int)PS,
-                          cur_stream()),
+  TORCH_CHECK(G >= 1 && G <= 8, "attn_verify: 1 <= G <= 8");
+  const DecodeStep c = check_decode_step(&qkv, kc, vc, {}, {}, slot0, attn_len0, kv_start, pos0, cos, sin, Hq, G, out,
+                                         "attn_verify");  // no scales: a bf16 cache
+  CHECK_ALIGN16(qkv); CHECK_ALIGN16(out);
+  TORCH_CHECK(!c.pos || pos0->numel() == c.B, "attn_verify: tables");
+  TORCH_CHECK(!(kv_start.has_value() && kv_start->defined()) || kv_start->numel() == c.B, "attn_verify: kv_start");
+  check_rc(rt_attn_verify(qkv.data_ptr(), qkv.stride(0), kc.data_ptr(), vc.data_ptr(), (int)c.Smax,
+                          slot0.data_ptr<int>(), attn_len0.data_ptr<int>(), (const int*)opt_ptr(kv_start), c.pos, c.cos,
+                          c.sin, (float)sign, (int)window, out.data_ptr(), out.stride(0), (int)c.B, (int)G, (int)Hq,
+                          (int)c.Hkv, (int)c.D, (float)scale, (int)PS, cur_stream()),
            "attn_verify");
 }
 

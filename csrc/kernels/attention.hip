@@ -565,9 +565,13 @@ struct DecodeFusedArgs {
   float* ksc; float* vsc; int SmaxP;
 };
 
+// rotary tables [P, D/2] (cosT null: no rotary) and the rotation's sign
+struct RopeTab {
+  const float* cosT; const float* sinT; float sign;
+};
+
 template <int D>
-__device__ __forceinline__ void rope_chunk(const bf16_t* head, int dl, const DecodeFusedArgs& a, int p,
-                                           float (&out)[8]) {
+__device__ __forceinline__ void rope_chunk(const bf16_t* head, int dl, const RopeTab& a, int p, float (&out)[8]) {
   constexpr int HALF = D / 16;  // chunks of 8 in half a head
   float x[8];
   unpack8(*(const uint4*)(head + dl * 8), x);
@@ -626,19 +630,10 @@ __device__ __forceinline__ void load_chunk(KVChunk<D, NK>& c, const bf16_t* kbas
 }
 
 template <int D, int G, int NK>
-__device__ __forceinline__ void consume_chunk(KVChunk<D, NK>& c, int c0, int p1, int s_new, bool has_new,
-                                              const uint4& kp, const uint4& vp, const float (&qv)[G][8],
+__device__ __forceinline__ void consume_chunk(const KVChunk<D, NK>& c, int c0, int p1, const float (&qv)[G][8],
                                               float (&m)[G], float (&l)[G], float (&acc)[G][8], int wid, int sub,
                                               float scale_log2) {
   constexpr int LPK = D / 8, KPW = 64 / LPK;
-  if (has_new) {
-    // compare the CLAMPED index load_chunk read: lanes past p1 re-read slot p1 - 1, which in a
-    // decode step is s_new itself — a slot this very launch is still writing (stale or
-    // uninitialised cache memory; masked, but 0 * NaN would poison the PV sum)
-#pragma unroll
-    for (int i = 0; i < NK; ++i)
-      if (min(c0 + (i * 4 + wid) * KPW + sub, p1 - 1) == s_new) { c.k[i] = kp; c.v[i] = vp; }
-  }
   float sc[G][NK];
 #pragma unroll
   for (int i = 0; i < NK; ++i) {
@@ -684,11 +679,117 @@ __device__ __forceinline__ void consume_chunk(KVChunk<D, NK>& c, int c0, int p1,
   }
 }
 
-template <int D, int G, int NK>
-__global__ __launch_bounds__(256) void attn_decode_fused_kernel(DecodeFusedArgs a) {
+// The VALU key walk of one partition [p0, p1) (p0 < p1) of a (batch, kv head) row by one 256-thread
+// workgroup: double-buffered chunk loads, per-lane online softmax (consume_chunk), then the merge of
+// lanes holding the same d (over sub within the wave) and of the 4 waves. The first two chunks are
+// issued before after_issue() runs: the caller rotates q into qv there (and whatever else waits on
+// its own loads), so waiting for q drains both chunks and a partition of <= 2 chunks (the batch-1
+// partition plan) costs one memory round trip, not two. patch(chunk, c0) replaces, in a freshly
+// loaded chunk, the rows that must not come from the cache (rows the launch itself appends).
+// Returns the partition's row maxima / sums in mrow / lrow and leaves wave w's unnormalised O sums
+// in red[(w * G + g) * D + d]. The decode step and the verify step both run this function: a query
+// row walks the same keys with the same arithmetic in either.
+template <int D, int G, int NK, class AfterIssue, class Patch>
+__device__ __forceinline__ void walk_partition(const bf16_t* kbase, const bf16_t* vbase, int p0, int p1, bool nt,
+                                               float (&qv)[G][8], float scale_log2, float (&red)[4 * G * D],
+                                               float (&wst)[4][G][2], AfterIssue&& after_issue, Patch&& patch,
+                                               float (&mrow)[G], float (&lrow)[G]) {
   constexpr int LPK = D / 8;    // lanes per key
   constexpr int KPW = 64 / LPK; // keys per wave-step
   constexpr int CH = 4 * KPW * NK;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int sub = lane / LPK, dl = lane % LPK;
+  KVChunk<D, NK> ca, cb;
+  load_chunk<D, NK>(ca, kbase, vbase, p0, p1, wid, sub, dl, nt);
+  if (p0 + CH < p1) load_chunk<D, NK>(cb, kbase, vbase, p0 + CH, p1, wid, sub, dl, nt);
+  after_issue();
+  float m[G], l[G], acc[G][8];
+#pragma unroll
+  for (int gg = 0; gg < G; ++gg) {
+    m[gg] = -INFINITY;
+    l[gg] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[gg][e] = 0.f;
+  }
+  for (int c0 = p0; c0 < p1; c0 += 2 * CH) {
+    if (c0 != p0 && c0 + CH < p1) load_chunk<D, NK>(cb, kbase, vbase, c0 + CH, p1, wid, sub, dl, nt);
+    patch(ca, c0);
+    consume_chunk<D, G, NK>(ca, c0, p1, qv, m, l, acc, wid, sub, scale_log2);
+    if (c0 + CH < p1) {
+      if (c0 + 2 * CH < p1) load_chunk<D, NK>(ca, kbase, vbase, c0 + 2 * CH, p1, wid, sub, dl, nt);
+      patch(cb, c0 + CH);
+      consume_chunk<D, G, NK>(cb, c0 + CH, p1, qv, m, l, acc, wid, sub, scale_log2);
+    }
+  }
+  // merge lanes holding the same d (different keys): over sub within the wave, then over waves
+#pragma unroll
+  for (int gg = 0; gg < G; ++gg) {
+    float mw = m[gg];
+#pragma unroll
+    for (int off = LPK; off < 64; off <<= 1) mw = fmaxf(mw, __shfl_xor(mw, off, 64));
+    const float r = (m[gg] == -INFINITY) ? 0.f : exp2f(m[gg] - mw);
+    l[gg] *= r;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[gg][e] *= r;
+    m[gg] = mw;
+    if (lane == 0) wst[wid][gg][0] = mw;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int gg = 0; gg < G; ++gg) {
+    mrow[gg] = fmaxf(fmaxf(wst[0][gg][0], wst[1][gg][0]), fmaxf(wst[2][gg][0], wst[3][gg][0]));
+    const float r = (m[gg] == -INFINITY) ? 0.f : exp2f(m[gg] - mrow[gg]);
+    float lsum = l[gg] * r;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[gg][e] *= r;
+#pragma unroll
+    for (int off = LPK; off < 64; off <<= 1) {
+      lsum += __shfl_xor(lsum, off, 64);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[gg][e] += __shfl_xor(acc[gg][e], off, 64);
+    }
+    if (sub == 0) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) red[(wid * G + gg) * D + dl * 8 + e] = acc[gg][e];
+    }
+    if (lane == 0) wst[wid][gg][1] = lsum;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int gg = 0; gg < G; ++gg) lrow[gg] = wst[0][gg][1] + wst[1][gg][1] + wst[2][gg][1] + wst[3][gg][1];
+}
+
+// (M, L, O) <- merge((M, L, O), (mq, lq, oq)) of two unnormalised softmax partials (row maximum,
+// row sum, one output element). An empty partial (mq = -inf: its o was never written) is skipped.
+// Every merge over key partitions runs these operations in this order.
+__device__ __forceinline__ void merge_partial(float& M, float& L, float& O, float mq, float lq, float oq) {
+  if (mq == -INFINITY) return;
+  const float Mn = fmaxf(M, mq);
+  const float r0 = exp2f(M - Mn), r1 = exp2f(mq - Mn);
+  L = L * r0 + lq * r1;
+  O = O * r0 + oq * r1;
+  M = Mn;
+}
+
+// The last-arriving partition's merge of a row's NP published records {o[D], m, l} (agent-scope
+// loads; record q of the row at rec + q * stride): the normalised output element d.
+template <int D>
+__device__ __forceinline__ float merge_partitions(const float* rec, int stride, int NP, int d) {
+  float M = -INFINITY, L = 0.f, O = 0.f;
+#pragma unroll 4
+  for (int q = 0; q < NP; ++q) {
+    const float* r = rec + (long)q * stride;
+    const float mq = __hip_atomic_load(r + D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const float lq = __hip_atomic_load(r + D + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const float oq = __hip_atomic_load(r + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    merge_partial(M, L, O, mq, lq, oq);
+  }
+  return L > 0.f ? O / L : 0.f;
+}
+
+template <int D, int G, int NK>
+__global__ __launch_bounds__(256) void attn_decode_fused_kernel(DecodeFusedArgs a) {
+  constexpr int LPK = D / 8, KPW = 64 / LPK;  // lanes per key, keys per wave-step
   __shared__ float red[4 * G * D];
   __shared__ float wst[4][G][2];
   __shared__ int flag;
@@ -707,82 +808,40 @@ __global__ __launch_bounds__(256) void attn_decode_fused_kernel(DecodeFusedArgs 
   float mrow[G], lrow[G];
   const bool active = p0 < p1;
   if (active) {
+    const RopeTab rt{a.cosT, a.sinT, a.sign};
     const int p = a.pos ? a.pos[b] : 0;
     const bf16_t* kbase = a.kc + ((long)b * a.Hkv + hk) * a.Smax * D;
     const bf16_t* vbase = a.vc + ((long)b * a.Hkv + hk) * a.Smax * D;
-    KVChunk<D, NK> ca, cb;
-    load_chunk<D, NK>(ca, kbase, vbase, p0, p1, wid, sub, dl, a.kv_nt);
-    // the second chunk is issued with the first, before q (waiting for q drains both): a
-    // partition of <= 2 chunks (the batch-1 partition plan) costs one memory round trip, not two
-    if (p0 + CH < p1) load_chunk<D, NK>(cb, kbase, vbase, p0 + CH, p1, wid, sub, dl, a.kv_nt);
-    float qv[G][8];
-#pragma unroll
-    for (int gg = 0; gg < G; ++gg) rope_chunk<D>(row + (long)(hk * G + gg) * D, dl, a, p, qv[gg]);
     const bool has_new = s_new >= p0 && s_new < p1;
     uint4 kp = make_uint4(0, 0, 0, 0), vp = kp;
-    if (has_new) {
-      float kn[8], vn[8];
-      rope_chunk<D>(row + (long)(a.Hq + hk) * D, dl, a, p, kn);
-      unpack8(*(const uint4*)(row + (long)(a.Hq + a.Hkv + hk) * D + dl * 8), vn);
-      kp = pack8(kn);
-      vp = pack8(vn);
-      if (wid == 0 && sub == 0) {
-        *(uint4*)(a.kc + (((long)b * a.Hkv + hk) * a.Smax + s_new) * D + dl * 8) = kp;
-        *(uint4*)(a.vc + (((long)b * a.Hkv + hk) * a.Smax + s_new) * D + dl * 8) = vp;
-      }
-    }
-    float m[G], l[G], acc[G][8];
+    float qv[G][8];
+    walk_partition<D, G, NK>(
+        kbase, vbase, p0, p1, a.kv_nt, qv, a.scale_log2, red, wst,
+        [&] {  // q rotated; the partition owning the new slot rotates k_new, appends k / v and keeps them
 #pragma unroll
-    for (int gg = 0; gg < G; ++gg) {
-      m[gg] = -INFINITY;
-      l[gg] = 0.f;
+          for (int gg = 0; gg < G; ++gg) rope_chunk<D>(row + (long)(hk * G + gg) * D, dl, rt, p, qv[gg]);
+          if (has_new) {
+            float kn[8], vn[8];
+            rope_chunk<D>(row + (long)(a.Hq + hk) * D, dl, rt, p, kn);
+            unpack8(*(const uint4*)(row + (long)(a.Hq + a.Hkv + hk) * D + dl * 8), vn);
+            kp = pack8(kn);
+            vp = pack8(vn);
+            if (wid == 0 && sub == 0) {
+              *(uint4*)(a.kc + (((long)b * a.Hkv + hk) * a.Smax + s_new) * D + dl * 8) = kp;
+              *(uint4*)(a.vc + (((long)b * a.Hkv + hk) * a.Smax + s_new) * D + dl * 8) = vp;
+            }
+          }
+        },
+        [&](KVChunk<D, NK>& c, int c0) {
+          if (!has_new) return;
+          // compare the CLAMPED index load_chunk read: lanes past p1 re-read slot p1 - 1, which in a
+          // decode step is s_new itself — a slot this very launch is still writing (stale or
+          // uninitialised cache memory; masked, but 0 * NaN would poison the PV sum)
 #pragma unroll
-      for (int e = 0; e < 8; ++e) acc[gg][e] = 0.f;
-    }
-    for (int c0 = p0; c0 < p1; c0 += 2 * CH) {
-      if (c0 != p0 && c0 + CH < p1) load_chunk<D, NK>(cb, kbase, vbase, c0 + CH, p1, wid, sub, dl, a.kv_nt);
-      consume_chunk<D, G, NK>(ca, c0, p1, s_new, has_new, kp, vp, qv, m, l, acc, wid, sub, a.scale_log2);
-      if (c0 + CH < p1) {
-        if (c0 + 2 * CH < p1) load_chunk<D, NK>(ca, kbase, vbase, c0 + 2 * CH, p1, wid, sub, dl, a.kv_nt);
-        consume_chunk<D, G, NK>(cb, c0 + CH, p1, s_new, has_new, kp, vp, qv, m, l, acc, wid, sub, a.scale_log2);
-      }
-    }
-    // merge lanes holding the same d (different keys): over sub within the wave, then over waves
-#pragma unroll
-    for (int gg = 0; gg < G; ++gg) {
-      float mw = m[gg];
-#pragma unroll
-      for (int off = LPK; off < 64; off <<= 1) mw = fmaxf(mw, __shfl_xor(mw, off, 64));
-      const float r = (m[gg] == -INFINITY) ? 0.f : exp2f(m[gg] - mw);
-      l[gg] *= r;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) acc[gg][e] *= r;
-      m[gg] = mw;
-      if (lane == 0) wst[wid][gg][0] = mw;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int gg = 0; gg < G; ++gg) {
-      mrow[gg] = fmaxf(fmaxf(wst[0][gg][0], wst[1][gg][0]), fmaxf(wst[2][gg][0], wst[3][gg][0]));
-      const float r = (m[gg] == -INFINITY) ? 0.f : exp2f(m[gg] - mrow[gg]);
-      float lsum = l[gg] * r;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) acc[gg][e] *= r;
-#pragma unroll
-      for (int off = LPK; off < 64; off <<= 1) {
-        lsum += __shfl_xor(lsum, off, 64);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[gg][e] += __shfl_xor(acc[gg][e], off, 64);
-      }
-      if (sub == 0) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) red[(wid * G + gg) * D + dl * 8 + e] = acc[gg][e];
-      }
-      if (lane == 0) wst[wid][gg][1] = lsum;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int gg = 0; gg < G; ++gg) lrow[gg] = wst[0][gg][1] + wst[1][gg][1] + wst[2][gg][1] + wst[3][gg][1];
+          for (int i = 0; i < NK; ++i)
+            if (min(c0 + (i * 4 + wid) * KPW + sub, p1 - 1) == s_new) { c.k[i] = kp; c.v[i] = vp; }
+        },
+        mrow, lrow);
   }
 
   if (a.NP == 1) {
@@ -827,21 +886,8 @@ __global__ __launch_bounds__(256) void attn_decode_fused_kernel(DecodeFusedArgs 
   if (!flag) return;
   for (int e = tid; e < G * D; e += 256) {
     const int gg = e / D, d = e % D;
-    float M = -INFINITY, L = 0.f, O = 0.f;
-#pragma unroll 4
-    for (int q = 0; q < a.NP; ++q) {
-      const float* r = pp + (q * G + gg) * (D + 2);
-      const float mq = __hip_atomic_load(r + D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const float lq = __hip_atomic_load(r + D + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const float oq = __hip_atomic_load(r + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (mq == -INFINITY) continue;  // empty partition: o[] never written
-      const float Mn = fmaxf(M, mq);
-      const float r0 = exp2f(M - Mn), r1 = exp2f(mq - Mn);
-      L = L * r0 + lq * r1;
-      O = O * r0 + oq * r1;
-      M = Mn;
-    }
-    a.o[(long)b * a.ldo + (long)(hk * G + gg) * D + d] = f2bf(L > 0.f ? O / L : 0.f);
+    a.o[(long)b * a.ldo + (long)(hk * G + gg) * D + d] =
+        f2bf(merge_partitions<D>(pp + gg * (D + 2), G * (D + 2), a.NP, d));
   }
   if (tid == 0) __hip_atomic_store(a.tickets + (long)b * a.Hkv + hk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -1112,8 +1158,10 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_g1_fp8_kernel(DecodeFused
 //     S^T accumulator, V through an LDS image (whole 256-B rows stored by ds_write_b128, read by
 //     ds_read_b64_tr_b16).
 // K and V of the next tile are prefetched into a second register set (plain loads only: no
-// LDS-DMA, so hipcc's counted waits keep the prefetch in flight; 178 VGPRs = 2 waves per SIMD:
-// all 2048 waves of a batch-256 layer are resident at once). The prologue issues every q / k_new /
+// LDS-DMA, so hipcc's counted waits keep the prefetch in flight; W = 1 compiles to 198-200 VGPRs
+// (fp8: 215-218) = 2 waves per SIMD: all 2048 waves of a batch-256 layer are resident at once;
+// W = 8 to 239-242 (fp8: 223-226), also 2, and W = 4 to 238 = 1: profiles/r8/
+// attn_decode_resources.txt). The prologue issues every q / k_new /
 // v_new / rotary-table load at once (one round trip) behind the first tile's loads. RoPE of q /
 // k_new and the cache append are fused; lanes whose (clamped) key is the new token's slot use
 // k_new / v_new from registers. Measured at batch 256 (Mistral-7B, 174..301 keys): 51 us per
@@ -1128,6 +1176,40 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_g1_fp8_kernel(DecodeFused
 // covering keys [part * PS, (part + 1) * PS) of the row; each publishes its merged (m, l, O) with
 // write-through stores and takes a ticket, and the last of the row's NP partitions merges them —
 // at 4k keys one workgroup per (batch, kv head) would stream 2 MB from one CU.
+// O += P·V of one 16-key tile (decode and verify MFMA kernels): P (A operand) = the packed S^T
+// accumulators, V (B operand) by transposed reads of the wave's V image (rows 16..31 zero)
+template <int D>
+__device__ __forceinline__ void pv_tile(const char* vimg, const bf16x8& pa, f32x4 (&o)[D / 16], int lane) {
+  const int g = lane >> 4, qrow_ = lane >> 2 & 3, pcol = lane & 3;
+#pragma unroll
+  for (int c = 0; c < D / 16; ++c) {
+    const int key_a = 4 * g + qrow_, col = 16 * c + 4 * pcol;
+    const s16x4 lo = ds_tr16(vimg + v_off<D>(key_a, col >> 3) + ((col & 7) << 1));
+    const s16x4 hi = ds_tr16(vimg + v_off<D>(key_a + 16, col >> 3) + ((col & 7) << 1));
+    o[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, cat_tr(lo, hi), o[c], 0, 0, 0);
+  }
+}
+
+// A wave's tiles cfirst, cfirst + cstep, ... below len with three in flight (ta, tb, tc hold the
+// first three on entry; all of a wave's tiles at up to 24 W keys: one memory round trip); a
+// register set is refilled right after its tile is consumed
+template <class Tile, class Load, class Consume>
+__device__ __forceinline__ void walk_tiles3(Tile& ta, Tile& tb, Tile& tc, int cfirst, int cstep, int len,
+                                            Load&& load, Consume&& consume) {
+  for (int c0 = cfirst; c0 < len; c0 += 3 * cstep) {
+    consume(ta, c0);
+    if (c0 + 3 * cstep < len) load(ta, c0 + 3 * cstep);
+    if (c0 + cstep < len) {
+      consume(tb, c0 + cstep);
+      if (c0 + 4 * cstep < len) load(tb, c0 + 4 * cstep);
+    }
+    if (c0 + 2 * cstep < len) {
+      consume(tc, c0 + 2 * cstep);
+      if (c0 + 5 * cstep < len) load(tc, c0 + 5 * cstep);
+    }
+  }
+}
+
 template <int G, int W, bool KV8 = false>
 __global__ __launch_bounds__(64 * W) void attn_decode_mfma_kernel(DecodeFusedArgs a) {
   constexpr int D = 128, DS = D / 32, DT = D / 16;
@@ -1422,16 +1504,7 @@ __global__ __launch_bounds__(64 * W) void attn_decode_mfma_kernel(DecodeFusedArg
 #pragma unroll
       for (int c = 0; c < DT; ++c) o[c][i] *= al;
     }
-    // O += P·V: P (A operand) = the packed S^T accumulators, V (B operand) by transposed reads
-    const bf16x8 pa = pack_bf16x8(st, f32x4{0.f, 0.f, 0.f, 0.f});
-    const int qrow_ = lane >> 2 & 3, pcol = lane & 3;
-#pragma unroll
-    for (int c = 0; c < DT; ++c) {
-      const int key_a = 4 * g + qrow_, col = 16 * c + 4 * pcol;
-      const s16x4 lo = ds_tr16(vimg + v_off<D>(key_a, col >> 3) + ((col & 7) << 1));
-      const s16x4 hi = ds_tr16(vimg + v_off<D>(key_a + 16, col >> 3) + ((col & 7) << 1));
-      o[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, cat_tr(lo, hi), o[c], 0, 0, 0);
-    }
+    pv_tile<D>(vimg, pack_bf16x8(st, f32x4{0.f, 0.f, 0.f, 0.f}), o, lane);
   };
 
   if constexpr (W == 1 && !DEEP8) {
@@ -1444,20 +1517,7 @@ __global__ __launch_bounds__(64 * W) void attn_decode_mfma_kernel(DecodeFusedArg
       }
     }
   } else {
-    // three tiles in flight (all of a wave's tiles at up to 24 W keys: one memory round trip);
-    // a register set is refilled right after its tile is consumed
-    for (int c0 = cfirst; c0 < len; c0 += 3 * cstep) {
-      consume(ta, c0);
-      if (c0 + 3 * cstep < len) load(ta, c0 + 3 * cstep);
-      if (c0 + cstep < len) {
-        consume(tb, c0 + cstep);
-        if (c0 + 4 * cstep < len) load(tb, c0 + 4 * cstep);
-      }
-      if (c0 + 2 * cstep < len) {
-        consume(tc, c0 + 2 * cstep);
-        if (c0 + 5 * cstep < len) load(tc, c0 + 5 * cstep);
-      }
-    }
+    walk_tiles3(ta, tb, tc, cfirst, cstep, len, load, consume);
   }
   if constexpr (W == 1) {
     // ---- normalise and store: lane holds O[head 4 g + i][d = 16 c + r16] ----
@@ -1531,21 +1591,8 @@ __global__ __launch_bounds__(64 * W) void attn_decode_mfma_kernel(DecodeFusedArg
       if (!last_flag) return;
       for (int e = threadIdx.x; e < G * D; e += 64 * W) {
         const int h = e / D, d = e % D;
-        float M = -INFINITY, L = 0.f, O = 0.f;
-#pragma unroll 4
-        for (int q = 0; q < NP; ++q) {
-          const float* r = pp + ((long)q * G + h) * (D + 2);
-          const float mq = __hip_atomic_load(r + D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (mq == -INFINITY) continue;  // empty partition: o[] never written
-          const float lq = __hip_atomic_load(r + D + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const float oq = __hip_atomic_load(r + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const float Mn = fmaxf(M, mq);
-          const float r0 = exp2f(M - Mn), r1 = exp2f(mq - Mn);
-          L = L * r0 + lq * r1;
-          O = O * r0 + oq * r1;
-          M = Mn;
-        }
-        a.o[(long)b * a.ldo + (long)(hk * G + h) * D + d] = f2bf(L > 0.f ? O / L : 0.f);
+        a.o[(long)b * a.ldo + (long)(hk * G + h) * D + d] =
+            f2bf(merge_partitions<D>(pp + h * (D + 2), G * (D + 2), NP, d));
       }
       if (threadIdx.x == 0) __hip_atomic_store(a.tickets + bh, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -1564,8 +1611,8 @@ __global__ __launch_bounds__(64 * W) void attn_decode_mfma_kernel(DecodeFusedArg
 // the query rows of ceil(G Q / 16) 16-row MFMA tiles; one workgroup of W waves per (batch, kv head,
 // row tile) streams the cache row once for its 16 query rows (Mistral-7B at K = 7: 32 rows, two
 // workgroups per kv head — a plain step at 8 rows streams eight cache rows from eight workgroups).
-// Wave w takes the 16-key tiles w, w + W, ... with three tiles in flight, exactly as
-// attn_decode_mfma_kernel<G, W > 1>; the S^T / P·V MFMA fragments and the V image are that kernel's,
+// Wave w takes the 16-key tiles w, w + W, ... with three tiles in flight, by the walk_tiles3 of
+// attn_decode_mfma_kernel<G, W > 1>; the S^T / P·V MFMA fragments (pv_tile) and the V image are that kernel's,
 // so a query row's arithmetic is that kernel's whenever the two walk the same 16-key tiles (no
 // window shorter than the sequence).
 //   * New rows: the workgroup rotates its query rows and all G new K rows (rope_chunk: the decode
@@ -1590,17 +1637,17 @@ struct VerifyArgs {
   int NP, PS;                       // head_dim 64 form: the decode step's key partitions (PS keys each)
 };
 
-template <int D, int W>
+template <int W>
 __global__ __launch_bounds__(64 * W) void attn_verify_mfma_kernel(VerifyArgs a) {
-  constexpr int NT = 1;  // one 16-row query tile per workgroup (blockIdx.y)
-  constexpr int DS = D / 32, DT = D / 16, CPR = D / 8, NVL = D / 32, GMAX = 8;
-  // per wave: V image (32 rows, 16..31 zero) while streaming, then its [16][D] fp32 O rows of a merge pass
+  // one 16-row query tile per workgroup (blockIdx.y); 16 chunks of 8 per row, 4 V chunks per lane and tile
+  constexpr int D = 128, DS = D / 32, DT = D / 16, CPR = D / 8, NVL = D / 32, GMAX = 8;
+  // per wave: V image (32 rows, 16..31 zero) while streaming, then its [16][D] fp32 O rows for the merge
   __shared__ __attribute__((aligned(16))) char vimg_all[W][32 * D * 2];
-  __shared__ __attribute__((aligned(16))) bf16_t qs[16 * NT * D];  // rotated query rows (zero past G * Q)
-  __shared__ __attribute__((aligned(16))) bf16_t kns[GMAX * D];    // rotated new K rows
-  __shared__ __attribute__((aligned(16))) bf16_t vns[GMAX * D];    // new V rows
-  __shared__ float mst[W][16 * NT], lst[W][16 * NT];
-  static_assert(32 * D * 2 == 16 * D * 4, "O rows of a merge pass reuse the V image");
+  __shared__ __attribute__((aligned(16))) bf16_t qs[16 * D];     // rotated query rows (zero past G * Q)
+  __shared__ __attribute__((aligned(16))) bf16_t kns[GMAX * D];  // rotated new K rows
+  __shared__ __attribute__((aligned(16))) bf16_t vns[GMAX * D];  // new V rows
+  __shared__ float mst[W][16], lst[W][16];
+  static_assert(32 * D * 2 == 16 * D * 4, "O rows of the merge reuse the V image");
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, r16 = lane & 15, w = tid >> 6;
   char* vimg = vimg_all[w];
   const int b = blockIdx.x / a.Hkv, hk = blockIdx.x % a.Hkv;
@@ -1642,9 +1689,8 @@ __global__ __launch_bounds__(64 * W) void attn_verify_mfma_kernel(VerifyArgs a) 
 
   // ---- rotate q rows and new K rows into LDS, copy new V rows; append K / V to the cache ----
   {
-    DecodeFusedArgs ra;
-    ra.cosT = a.cosT; ra.sinT = a.sinT; ra.sign = a.sign;
-    constexpr int NQ = 16 * NT * CPR, NKV = GMAX * CPR;
+    const RopeTab rt{a.cosT, a.sinT, a.sign};
+    constexpr int NQ = 16 * CPR, NKV = GMAX * CPR;
     for (int ch = tid; ch < NQ + 2 * NKV; ch += 64 * W) {
       uint4 val = make_uint4(0, 0, 0, 0);
       if (ch < NQ) {
@@ -1652,7 +1698,7 @@ __global__ __launch_bounds__(64 * W) void attn_verify_mfma_kernel(VerifyArgs a) 
         if (row < R) {
           const int j = row >> a.qshift, hq = row & (Q - 1);
           float f[8];
-          rope_chunk<D>(a.qkv + (row0 + j) * a.ldq + (long)(hk * Q + hq) * D, dl, ra, p0 + j, f);
+          rope_chunk<D>(a.qkv + (row0 + j) * a.ldq + (long)(hk * Q + hq) * D, dl, rt, p0 + j, f);
           val = pack8(f);
         }
         *(uint4*)(qs + (row - rbase) * D + dl * 8) = val;
@@ -1666,7 +1712,7 @@ __global__ __launch_bounds__(64 * W) void attn_verify_mfma_kernel(VerifyArgs a) 
             val = *(const uint4*)(src + (long)(a.Hq + a.Hkv + hk) * D + dl * 8);
           } else {
             float f[8];
-            rope_chunk<D>(src + (long)(a.Hq + hk) * D, dl, ra, p0 + j, f);
+            rope_chunk<D>(src + (long)(a.Hq + hk) * D, dl, rt, p0 + j, f);
             val = pack8(f);
           }
           if (blockIdx.y == 0 && s0 >= 0 && s0 + j < a.Smax) {
@@ -1686,26 +1732,17 @@ __global__ __launch_bounds__(64 * W) void attn_verify_mfma_kernel(VerifyArgs a) 
   }
   __syncthreads();
 
-  // visible keys [klo, khi) of this lane's query row of every row tile (row 16 t + r16)
-  int klo[NT], khi[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int row = rbase + 16 * t + r16, j = row >> a.qshift;
-    const int lj = len0 + j;
-    int lo = kstart;
-    if (a.window > 0) lo = max(lo, lj - a.window);
-    klo[t] = row < R ? lo : 0;
-    khi[t] = row < R ? min(min(lj, s0 + j + 1), len) : 0;  // new row i (key s0 + i) only for i <= j
+  // visible keys [klo, khi) of this lane's query row (row r16 of the tile)
+  int klo = 0, khi = 0;
+  if (rbase + r16 < R) {
+    const int j = (rbase + r16) >> a.qshift, lj = len0 + j;
+    klo = a.window > 0 ? max(kstart, lj - a.window) : kstart;
+    khi = min(min(lj, s0 + j + 1), len);  // new row i (key s0 + i) only for i <= j
   }
-  f32x4 o[NT][DT];
-  float m[NT], l[NT];
+  f32x4 o[DT];
 #pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    m[t] = -INFINITY;
-    l[t] = 0.f;
-#pragma unroll
-    for (int c = 0; c < DT; ++c) o[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
+  for (int c = 0; c < DT; ++c) o[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.f;
 
   bf16x8 qf[DS];  // B operand of S^T = K·Q^T: Q[row r16][32 s + 8 g ..]
 #pragma unroll
@@ -1737,123 +1774,89 @@ __global__ __launch_bounds__(64 * W) void attn_verify_mfma_kernel(VerifyArgs a) 
       const int f = 64 * i + lane;
       *(uint4*)(vimg + v_off<D>(f / CPR, f % CPR)) = vf[i];
     }
-    bf16x8 pa[NT];
+    // S^T: lane holds the scores of keys c0 + 4 g + i for query row r16
+    f32x4 st = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      // S^T: lane holds the scores of keys c0 + 4 g + i for query row 16 t + r16
-      f32x4 st = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int s2 = 0; s2 < DS; ++s2)
+      st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf[s2]), qf[s2], st, 0, 0, 0);
+    float mx = -INFINITY;
 #pragma unroll
-      for (int s2 = 0; s2 < DS; ++s2)
-        st = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf[s2]), qf[s2], st, 0, 0, 0);
-      float mx = -INFINITY;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int key = c0 + 4 * g + i;
-        const float x = (key >= klo[t] && key < khi[t]) ? st[i] * a.scale_log2 : -INFINITY;
-        st[i] = x;
-        mx = fmaxf(mx, x);
-      }
-      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      const float mn = fmaxf(m[t], mx);
-      const float ms = mn == -INFINITY ? 0.f : mn;  // nothing visible yet: every exponent below is -inf
-      const float alpha = exp2f(m[t] - ms);         // m = -inf: 0 (O and l are still 0)
-      m[t] = mn;
-      float rs = 0.f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float pv = exp2f(st[i] - ms);
-        st[i] = pv;
-        rs += pv;
-      }
-      rs += __shfl_xor(rs, 16, 64);
-      rs += __shfl_xor(rs, 32, 64);
-      l[t] = l[t] * alpha + rs;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float al = __shfl(alpha, 4 * g + i, 64);
-#pragma unroll
-        for (int c = 0; c < DT; ++c) o[t][c][i] *= al;
-      }
-      pa[t] = pack_bf16x8(st, f32x4{0.f, 0.f, 0.f, 0.f});
+    for (int i = 0; i < 4; ++i) {
+      const int key = c0 + 4 * g + i;
+      const float x = (key >= klo && key < khi) ? st[i] * a.scale_log2 : -INFINITY;
+      st[i] = x;
+      mx = fmaxf(mx, x);
     }
-    // O += P·V: P (A operand) = the packed S^T accumulators, V (B operand) by transposed reads
-    const int qrow_ = lane >> 2 & 3, pcol = lane & 3;
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float mn = fmaxf(m, mx);
+    const float ms = mn == -INFINITY ? 0.f : mn;  // nothing visible yet: every exponent below is -inf
+    const float alpha = exp2f(m - ms);            // m = -inf: 0 (O and l are still 0)
+    m = mn;
+    float rs = 0.f;
 #pragma unroll
-    for (int c = 0; c < DT; ++c) {
-      const int key_a = 4 * g + qrow_, col = 16 * c + 4 * pcol;
-      const s16x4 lo = ds_tr16(vimg + v_off<D>(key_a, col >> 3) + ((col & 7) << 1));
-      const s16x4 hi = ds_tr16(vimg + v_off<D>(key_a + 16, col >> 3) + ((col & 7) << 1));
-      const bf16x8 vfr = cat_tr(lo, hi);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) o[t][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa[t], vfr, o[t][c], 0, 0, 0);
+    for (int i = 0; i < 4; ++i) {
+      const float pv = exp2f(st[i] - ms);
+      st[i] = pv;
+      rs += pv;
     }
+    rs += __shfl_xor(rs, 16, 64);
+    rs += __shfl_xor(rs, 32, 64);
+    l = l * alpha + rs;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float al = __shfl(alpha, 4 * g + i, 64);
+#pragma unroll
+      for (int c = 0; c < DT; ++c) o[c][i] *= al;
+    }
+    pv_tile<D>(vimg, pack_bf16x8(st, f32x4{0.f, 0.f, 0.f, 0.f}), o, lane);
   };
+  walk_tiles3(ta, tb, tc, cfirst, cstep, len, load, consume);
 
-  for (int c0 = cfirst; c0 < len; c0 += 3 * cstep) {
-    consume(ta, c0);
-    if (c0 + 3 * cstep < len) load(ta, c0 + 3 * cstep);
-    if (c0 + cstep < len) {
-      consume(tb, c0 + cstep);
-      if (c0 + 4 * cstep < len) load(tb, c0 + 4 * cstep);
-    }
-    if (c0 + 2 * cstep < len) {
-      consume(tc, c0 + 2 * cstep);
-      if (c0 + 5 * cstep < len) load(tc, c0 + 5 * cstep);
-    }
-  }
-
-  // ---- merge the W waves' states, one row tile per pass (m = -inf, l = 0 for a wave without tiles).
-  // A wave's O rows go to its own V-image region (its transposed reads precede them in its LDS queue)
+  // ---- merge the W waves' states (m = -inf, l = 0 for a wave without tiles). A wave's O rows go
+  // to its own V-image region (its transposed reads precede them in its LDS queue)
   if (g == 0) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      mst[w][16 * t + r16] = m[t];
-      lst[w][16 * t + r16] = l[t];
-    }
+    mst[w][r16] = m;
+    lst[w][r16] = l;
   }
   float* ost = (float*)vimg_all[0];  // [W][16][D]
 #pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    if (t > 0) __syncthreads();  // the previous pass has been read
+  for (int i = 0; i < 4; ++i) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int c = 0; c < DT; ++c) ost[(w * 16 + 4 * g + i) * D + 16 * c + r16] = o[c][i];
+  }
+  __syncthreads();
+  for (int e = tid; e < 16 * D; e += 64 * W) {
+    const int h = e / D, d = e % D;
+    if (rbase + h >= R) continue;
+    float M = -INFINITY;
 #pragma unroll
-      for (int c = 0; c < DT; ++c) ost[(w * 16 + 4 * g + i) * D + 16 * c + r16] = o[t][c][i];
-    }
-    __syncthreads();
-    for (int e = tid; e < 16 * D; e += 64 * W) {
-      const int h = e / D, d = e % D, row = 16 * t + h;
-      if (rbase + row >= R) continue;
-      float M = -INFINITY;
+    for (int q = 0; q < W; ++q) M = fmaxf(M, mst[q][h]);
+    float L = 0.f, O = 0.f;
+    if (M != -INFINITY) {
 #pragma unroll
-      for (int q = 0; q < W; ++q) M = fmaxf(M, mst[q][row]);
-      float L = 0.f, O = 0.f;
-      if (M != -INFINITY) {
-#pragma unroll
-        for (int q = 0; q < W; ++q) {
-          const float mq = mst[q][row];
-          if (mq == -INFINITY) continue;
-          const float f = exp2f(mq - M);
-          L += lst[q][row] * f;
-          O += ost[(q * 16 + h) * D + d] * f;
-        }
+      for (int q = 0; q < W; ++q) {
+        const float mq = mst[q][h];
+        if (mq == -INFINITY) continue;
+        const float f = exp2f(mq - M);
+        L += lst[q][h] * f;
+        O += ost[(q * 16 + h) * D + d] * f;
       }
-      const int j = (rbase + row) >> a.qshift, hq = (rbase + row) & (Q - 1);
-      a.o[(row0 + j) * a.ldo + (long)(hk * Q + hq) * D + d] = f2bf(L > 0.f ? O / L : 0.f);
     }
+    const int j = (rbase + h) >> a.qshift, hq = (rbase + h) & (Q - 1);
+    a.o[(row0 + j) * a.ldo + (long)(hk * Q + hq) * D + d] = f2bf(L > 0.f ? O / L : 0.f);
   }
 }
 
 // Head dims the decode step runs on attn_decode_fused_kernel (D = 64: the tiny presets): the verify
 // step is that kernel's arithmetic, position by position, in one launch. Workgroup (j, kv head,
-// batch) walks position j's keys [kbeg_j, len_j) with the decode kernel's own chunk loads, chunk
-// consumption (consume_chunk), lane / wave merges and partition merge (partitions of a.PS keys,
-// walked in order by the one workgroup and merged with the last arriver's formulas), so its output
+// batch) walks position j's keys [kbeg_j, len_j) by calling the decode kernel's own partition walk
+// (walk_partition: chunk loads, consume_chunk, lane / wave merges) once per partition of a.PS keys,
+// in order, and folds the partitions with the last arriver's step (merge_partial), so its output
 // is bitwise that of the j-th of G successive decode steps, and greedy verify output is greedy
 // decode output, token for token. The new rows 0..j are rotated by the workgroup itself into LDS
-// (rope_chunk) and substituted into the loaded chunks by clamped key, as consume_chunk does for its
-// one new row: nothing the launch appends is read back. Workgroup j alone stores row j. The cache row
+// (rope_chunk) and substituted into the loaded chunks by clamped key, as the decode kernel does for
+// its one new row: nothing the launch appends is read back. Workgroup j alone stores row j. The cache row
 // is read G times here (from L2 after the first): these shapes are test-sized, the streamed-once
 // form is the MFMA kernel above.
 template <int D, int G, int NK>
@@ -1876,8 +1879,7 @@ __global__ __launch_bounds__(256) void attn_verify_valu_kernel(VerifyArgs a) {
   const bf16_t* row = a.qkv + ((long)b * a.G + j) * a.ldq;
   const bf16_t* kbase = a.kc + ((long)b * a.Hkv + hk) * a.Smax * D;
   const bf16_t* vbase = a.vc + ((long)b * a.Hkv + hk) * a.Smax * D;
-  DecodeFusedArgs ra;
-  ra.cosT = a.cosT; ra.sinT = a.sinT; ra.sign = a.sign;
+  const RopeTab rt{a.cosT, a.sinT, a.sign};
   // new rows 0..j -> LDS (thread = one 8-element chunk of one row's K or V); row j -> cache
   if (tid < 2 * GMAX * LPK) {
     const bool isv = tid >= GMAX * LPK;
@@ -1889,7 +1891,7 @@ __global__ __launch_bounds__(256) void attn_verify_valu_kernel(VerifyArgs a) {
         val = *(const uint4*)(src + (long)(a.Hq + a.Hkv + hk) * D + c * 8);
       } else {
         float kn[8];
-        rope_chunk<D>(src + (long)(a.Hq + hk) * D, c, ra, p - j + i, kn);
+        rope_chunk<D>(src + (long)(a.Hq + hk) * D, c, rt, p - j + i, kn);
         val = pack8(kn);
       }
       if (i == j && s_new >= 0 && s_new < a.Smax)
@@ -1899,88 +1901,33 @@ __global__ __launch_bounds__(256) void attn_verify_valu_kernel(VerifyArgs a) {
   }
   float qv[G][8];
 #pragma unroll
-  for (int gg = 0; gg < G; ++gg) rope_chunk<D>(row + (long)(hk * G + gg) * D, dl, ra, p, qv[gg]);
+  for (int gg = 0; gg < G; ++gg) rope_chunk<D>(row + (long)(hk * G + gg) * D, dl, rt, p, qv[gg]);
   __syncthreads();
 
   float Mr[EPT], Lr[EPT], Or[EPT];
 #pragma unroll
   for (int x = 0; x < EPT; ++x) { Mr[x] = -INFINITY; Lr[x] = 0.f; Or[x] = 0.f; }
-  const uint4 zero4 = make_uint4(0, 0, 0, 0);
   for (int part = 0; part < a.NP; ++part) {
     const int p0 = max(part * a.PS, kbeg), p1 = min((part + 1) * a.PS, len);
     const bool active = p0 < p1;
     float mrow[G], lrow[G];
     if (active) {
-      // keys at or above slot0 (clamped index, as the loads) are this launch's new rows: from LDS
-      auto subst = [&](KVChunk<D, NK>& c, int c0) {
-        if (c0 + CH <= s0 && p1 - 1 < s0) return;
+      // the decode kernel's walk (q is rotated already); keys at or above slot0 (clamped index, as
+      // the loads) are this launch's new rows: from LDS
+      walk_partition<D, G, NK>(
+          kbase, vbase, p0, p1, true, qv, a.scale_log2, red, wst, [] {},
+          [&](KVChunk<D, NK>& c, int c0) {
+            if (c0 + CH <= s0 && p1 - 1 < s0) return;
 #pragma unroll
-        for (int i = 0; i < NK; ++i) {
-          const int jn = min(c0 + (i * 4 + wid) * KPW + sub, p1 - 1) - s0;
-          if (jn >= 0 && jn <= j) {
-            c.k[i] = *(const uint4*)(kns + jn * D + dl * 8);
-            c.v[i] = *(const uint4*)(vns + jn * D + dl * 8);
-          }
-        }
-      };
-      KVChunk<D, NK> ca, cb;
-      load_chunk<D, NK>(ca, kbase, vbase, p0, p1, wid, sub, dl, true);
-      if (p0 + CH < p1) load_chunk<D, NK>(cb, kbase, vbase, p0 + CH, p1, wid, sub, dl, true);
-      float m[G], l[G], acc[G][8];
-#pragma unroll
-      for (int gg = 0; gg < G; ++gg) {
-        m[gg] = -INFINITY;
-        l[gg] = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[gg][e] = 0.f;
-      }
-      for (int c0 = p0; c0 < p1; c0 += 2 * CH) {
-        if (c0 != p0 && c0 + CH < p1) load_chunk<D, NK>(cb, kbase, vbase, c0 + CH, p1, wid, sub, dl, true);
-        subst(ca, c0);
-        consume_chunk<D, G, NK>(ca, c0, p1, s_new, false, zero4, zero4, qv, m, l, acc, wid, sub, a.scale_log2);
-        if (c0 + CH < p1) {
-          if (c0 + 2 * CH < p1) load_chunk<D, NK>(ca, kbase, vbase, c0 + 2 * CH, p1, wid, sub, dl, true);
-          subst(cb, c0 + CH);
-          consume_chunk<D, G, NK>(cb, c0 + CH, p1, s_new, false, zero4, zero4, qv, m, l, acc, wid, sub,
-                                  a.scale_log2);
-        }
-      }
-      // the decode kernel's merges: over sub within the wave, then over the 4 waves
-#pragma unroll
-      for (int gg = 0; gg < G; ++gg) {
-        float mw = m[gg];
-#pragma unroll
-        for (int off = LPK; off < 64; off <<= 1) mw = fmaxf(mw, __shfl_xor(mw, off, 64));
-        const float r = (m[gg] == -INFINITY) ? 0.f : exp2f(m[gg] - mw);
-        l[gg] *= r;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[gg][e] *= r;
-        m[gg] = mw;
-        if (lane == 0) wst[wid][gg][0] = mw;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int gg = 0; gg < G; ++gg) {
-        mrow[gg] = fmaxf(fmaxf(wst[0][gg][0], wst[1][gg][0]), fmaxf(wst[2][gg][0], wst[3][gg][0]));
-        const float r = (m[gg] == -INFINITY) ? 0.f : exp2f(m[gg] - mrow[gg]);
-        float lsum = l[gg] * r;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[gg][e] *= r;
-#pragma unroll
-        for (int off = LPK; off < 64; off <<= 1) {
-          lsum += __shfl_xor(lsum, off, 64);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc[gg][e] += __shfl_xor(acc[gg][e], off, 64);
-        }
-        if (sub == 0) {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) red[(wid * G + gg) * D + dl * 8 + e] = acc[gg][e];
-        }
-        if (lane == 0) wst[wid][gg][1] = lsum;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int gg = 0; gg < G; ++gg) lrow[gg] = wst[0][gg][1] + wst[1][gg][1] + wst[2][gg][1] + wst[3][gg][1];
+            for (int i = 0; i < NK; ++i) {
+              const int jn = min(c0 + (i * 4 + wid) * KPW + sub, p1 - 1) - s0;
+              if (jn >= 0 && jn <= j) {
+                c.k[i] = *(const uint4*)(kns + jn * D + dl * 8);
+                c.v[i] = *(const uint4*)(vns + jn * D + dl * 8);
+              }
+            }
+          },
+          mrow, lrow);
     }
 #pragma unroll
     for (int x = 0; x < EPT; ++x) {
@@ -1997,12 +1944,8 @@ __global__ __launch_bounds__(256) void attn_verify_valu_kernel(VerifyArgs a) {
       if (a.NP == 1) {  // the decode kernel's single-partition store
         Or[x] = (active && lq > 0.f) ? osum / lq : 0.f;
         Lr[x] = -1.f;
-      } else if (mq != -INFINITY) {  // its last arriver's merge, partitions in order
-        const float Mn = fmaxf(Mr[x], mq);
-        const float r0 = exp2f(Mr[x] - Mn), r1 = exp2f(mq - Mn);
-        Lr[x] = Lr[x] * r0 + lq * r1;
-        Or[x] = Or[x] * r0 + osum * r1;
-        Mr[x] = Mn;
+      } else {  // its last arriver's merge, partitions in order
+        merge_partial(Mr[x], Lr[x], Or[x], mq, lq, osum);
       }
     }
     __syncthreads();  // red / wst are rewritten by the next partition
@@ -2048,7 +1991,7 @@ extern "C" int rt_attn_verify(const void* qkv, long ldq, void* kc, void* vc, int
   }
   // 8 waves per (batch, kv head, 16-row query tile), as the decode kernel's small-batch form
   dim3 grid((unsigned)(B * Hkv), (unsigned)((G * Q + 15) / 16));
-  hipLaunchKernelGGL((attn_verify_mfma_kernel<128, 8>), grid, dim3(64 * 8), 0, stream, a);
+  hipLaunchKernelGGL(attn_verify_mfma_kernel<8>, grid, dim3(64 * 8), 0, stream, a);
   RT_LAUNCH_CHECK();
   return 0;
 }
@@ -2590,6 +2533,25 @@ extern "C" int rt_kv_store_fp8(const void* qkv, long ldq, void* kc, void* vc, fl
   return 0;
 }
 
+// attn_decode_mfma_kernel<G, W, KV8> on `blocks` workgroups of W waves; the caller has checked G
+// (1, 2, 4, 8; 16 exists only for the one-wave bf16 form, which rt_attn_decode_mfma_ok alone admits)
+template <int W, bool KV8>
+static void launch_decode_mfma(int G, int blocks, const DecodeFusedArgs& a, hipStream_t stream) {
+  const dim3 grid((unsigned)blocks), block(64 * W);
+  if constexpr (W == 1 && !KV8) {
+    if (G == 16) {
+      hipLaunchKernelGGL((attn_decode_mfma_kernel<16, 1, false>), grid, block, 0, stream, a);
+      return;
+    }
+  }
+  switch (G) {
+    case 1: hipLaunchKernelGGL((attn_decode_mfma_kernel<1, W, KV8>), grid, block, 0, stream, a); break;
+    case 2: hipLaunchKernelGGL((attn_decode_mfma_kernel<2, W, KV8>), grid, block, 0, stream, a); break;
+    case 4: hipLaunchKernelGGL((attn_decode_mfma_kernel<4, W, KV8>), grid, block, 0, stream, a); break;
+    default: hipLaunchKernelGGL((attn_decode_mfma_kernel<8, W, KV8>), grid, block, 0, stream, a); break;
+  }
+}
+
 extern "C" int rt_attn_decode_fused(const void* qkv, long ldq, void* kc, void* vc, int Smax, const int* slot,
                                     const int* attn_len, const int* kv_start, const int* pos, const float* cosT,
                                     const float* sinT, float sign, int window, float* part, unsigned* tickets, int NP,
@@ -2625,82 +2587,41 @@ extern "C" int rt_attn_decode_fused(const void* qkv, long ldq, void* kc, void* v
       RT_LAUNCH_CHECK();
       return 0;
     }
-    if (rt_attn_decode_mfma_ok(B, Hq, Hkv, D, NP)) {
-      dim3 mgrid((unsigned)(B * Hkv)), mblock(64);
-      switch (G) {
-        case 1: hipLaunchKernelGGL((attn_decode_mfma_kernel<1, 1, true>), mgrid, mblock, 0, stream, a); break;
-        case 2: hipLaunchKernelGGL((attn_decode_mfma_kernel<2, 1, true>), mgrid, mblock, 0, stream, a); break;
-        case 4: hipLaunchKernelGGL((attn_decode_mfma_kernel<4, 1, true>), mgrid, mblock, 0, stream, a); break;
-        default: hipLaunchKernelGGL((attn_decode_mfma_kernel<8, 1, true>), mgrid, mblock, 0, stream, a); break;
-      }
-    } else {
-      if (NP > 1 && !(part && tickets)) return -3;
-      const int npm = rt_attn_decode_mw_np(Smax, NP);
-      a.NP = npm;
-      a.PS = npm > 1 ? ((Smax + npm - 1) / npm + 15) / 16 * 16 : Smax;
-      dim3 mgrid((unsigned)(B * Hkv * npm)), mblock(64 * DEC_MW);
-      switch (G) {
-        case 1: hipLaunchKernelGGL((attn_decode_mfma_kernel<1, DEC_MW, true>), mgrid, mblock, 0, stream, a); break;
-        case 2: hipLaunchKernelGGL((attn_decode_mfma_kernel<2, DEC_MW, true>), mgrid, mblock, 0, stream, a); break;
-        case 4: hipLaunchKernelGGL((attn_decode_mfma_kernel<4, DEC_MW, true>), mgrid, mblock, 0, stream, a); break;
-        default: hipLaunchKernelGGL((attn_decode_mfma_kernel<8, DEC_MW, true>), mgrid, mblock, 0, stream, a); break;
-      }
-    }
-    RT_LAUNCH_CHECK();
-    return 0;
   }
-  // large batch, one partition per (batch, kv head): the MFMA kernel
+  // large batch, one partition per (batch, kv head): the one-wave MFMA kernel
   if (rt_attn_decode_mfma_ok(B, Hq, Hkv, D, NP)) {
-    dim3 mgrid((unsigned)(B * Hkv)), mblock(64);
-    switch (G) {
-      case 1: hipLaunchKernelGGL((attn_decode_mfma_kernel<1, 1>), mgrid, mblock, 0, stream, a); break;
-      case 2: hipLaunchKernelGGL((attn_decode_mfma_kernel<2, 1>), mgrid, mblock, 0, stream, a); break;
-      case 4: hipLaunchKernelGGL((attn_decode_mfma_kernel<4, 1>), mgrid, mblock, 0, stream, a); break;
-      case 8: hipLaunchKernelGGL((attn_decode_mfma_kernel<8, 1>), mgrid, mblock, 0, stream, a); break;
-      default: hipLaunchKernelGGL((attn_decode_mfma_kernel<16, 1>), mgrid, mblock, 0, stream, a); break;
-    }
+    if (kv8) launch_decode_mfma<1, true>(G, B * Hkv, a, stream);
+    else launch_decode_mfma<1, false>(G, B * Hkv, a, stream);
     RT_LAUNCH_CHECK();
     return 0;
   }
-  // small batch, short caches: 8 waves per (batch, kv head), merged in LDS
-  if (rt_attn_decode_mw_ok(B, Hq, Hkv, D, Smax) && !a.qkv_slabs && (NP <= 1 || (part && tickets))) {
+  // small batch: W waves per (batch, kv head), merged in LDS; long caches in npm key partitions
+  // (fp8: every remaining shape; bf16: short of the slab form and of shapes the VALU kernel keeps)
+  if (kv8 && NP > 1 && !(part && tickets)) return -3;
+  if (kv8 || (rt_attn_decode_mw_ok(B, Hq, Hkv, D, Smax) && !a.qkv_slabs && (NP <= 1 || (part && tickets)))) {
     const int npm = rt_attn_decode_mw_np(Smax, NP);
     a.NP = npm;
     a.PS = npm > 1 ? ((Smax + npm - 1) / npm + 15) / 16 * 16 : Smax;
-    // 8 waves per (row, kv head) up to 256 pairs (one 512-thread workgroup per CU); 4 waves above
-    // (serving at batch 32..127: 1024-2048 waves instead of one chain of tiles per pair)
-    const bool w4 = (long)B * Hkv >= 256;
-    dim3 mgrid((unsigned)(B * Hkv * npm)), mblock(64 * (w4 ? 4 : DEC_MW));
-    if (w4) {
-      switch (G) {
-        case 1: hipLaunchKernelGGL((attn_decode_mfma_kernel<1, 4>), mgrid, mblock, 0, stream, a); break;
-        case 2: hipLaunchKernelGGL((attn_decode_mfma_kernel<2, 4>), mgrid, mblock, 0, stream, a); break;
-        case 4: hipLaunchKernelGGL((attn_decode_mfma_kernel<4, 4>), mgrid, mblock, 0, stream, a); break;
-        default: hipLaunchKernelGGL((attn_decode_mfma_kernel<8, 4>), mgrid, mblock, 0, stream, a); break;
-      }
-    } else {
-      switch (G) {
-        case 1: hipLaunchKernelGGL((attn_decode_mfma_kernel<1, DEC_MW>), mgrid, mblock, 0, stream, a); break;
-        case 2: hipLaunchKernelGGL((attn_decode_mfma_kernel<2, DEC_MW>), mgrid, mblock, 0, stream, a); break;
-        case 4: hipLaunchKernelGGL((attn_decode_mfma_kernel<4, DEC_MW>), mgrid, mblock, 0, stream, a); break;
-        default: hipLaunchKernelGGL((attn_decode_mfma_kernel<8, DEC_MW>), mgrid, mblock, 0, stream, a); break;
-      }
-    }
+    // 8 waves per (row, kv head) up to 256 pairs (one 512-thread workgroup per CU); bf16: 4 waves
+    // above (serving at batch 32..127: 1024-2048 waves instead of one chain of tiles per pair)
+    if (kv8) launch_decode_mfma<DEC_MW, true>(G, B * Hkv * npm, a, stream);
+    else if ((long)B * Hkv >= 256) launch_decode_mfma<4, false>(G, B * Hkv * npm, a, stream);
+    else launch_decode_mfma<DEC_MW, false>(G, B * Hkv * npm, a, stream);
     RT_LAUNCH_CHECK();
     return 0;
   }
   if (a.qkv_slabs) return -2;  // the slab form exists only in the MFMA kernel (caller reduces first)
-  const int nk = 4;  // keys per lane per chunk; PS must be a multiple of the chunk
-  if (PS % (4 * (64 / (D / 8)) * nk) != 0) return -1;
+  constexpr int NK = 4;  // keys per lane per chunk; PS must be a multiple of the chunk
+  if (PS % (4 * (64 / (D / 8)) * NK) != 0) return -1;
   dim3 grid(NP, Hkv, B), block(256);
-#define DF_CASE(DD, GG, NN)                                                                   \
-  if (D == DD && G == GG && nk == NN) {                                                       \
-    hipLaunchKernelGGL((attn_decode_fused_kernel<DD, GG, NN>), grid, block, 0, stream, a);    \
+#define DF_CASE(DD, GG)                                                                       \
+  if (D == DD && G == GG) {                                                                   \
+    hipLaunchKernelGGL((attn_decode_fused_kernel<DD, GG, NK>), grid, block, 0, stream, a);    \
     RT_LAUNCH_CHECK();                                                                        \
     return 0;                                                                                 \
   }
-#define DF_G(DD, NN) DF_CASE(DD, 1, NN) DF_CASE(DD, 2, NN) DF_CASE(DD, 4, NN) DF_CASE(DD, 8, NN)
-  DF_G(128, 4) DF_G(64, 4) DF_G(32, 4)
+#define DF_G(DD) DF_CASE(DD, 1) DF_CASE(DD, 2) DF_CASE(DD, 4) DF_CASE(DD, 8)
+  DF_G(128) DF_G(64) DF_G(32)
 #undef DF_G
 #undef DF_CASE
   return -1;
