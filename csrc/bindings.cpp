@@ -38,6 +38,10 @@ int rt_gemm_big_fp8(const void*, long, const float*, const void*, long, const fl
 int rt_gemm_fp8(const void*, long, const float*, const void*, long, const float*, const void*, void*, long, int, int,
                 int, int, int, float*, unsigned*, const void*, long, float, int, hipStream_t);
 int rt_quant_fp8_rows(const void*, long, void*, long, float*, long, int, hipStream_t);
+int rt_quant_mxfp4(const void*, void*, void*, long, long, hipStream_t);
+int rt_shuffle_decode_weight_fp4(const void*, const void*, void*, void*, long, long, hipStream_t);
+int rt_gemv_fp4(const void*, long, const void*, const void*, const void*, void*, long, int, int, int, int, int,
+                const void*, long, float, hipStream_t);
 int rt_norm_fwd(int, const void*, const void*, const void*, const void*, void*, void*, float*, float*, int, int, float,
                 const float*, int, hipStream_t);
 int rt_norm_bwd(int, const void*, const void*, const void*, const float*, const float*, const void*, void*, float*,
@@ -652,6 +656,98 @@ Tensor gemm_fp8(const Tensor& a, const optional<Tensor>& sa, const Tensor& wq, c
                        has_res ? residual->data_ptr() : nullptr, has_res ? residual->stride(0) : 0, (float)norm_eps,
                        w_shuffled ? 1 : 0, st),
            "gemm_fp8");
+  return c;
+}
+
+// ---------------------------------------------------------------------------------------------
+// MXFP4 (OCP MX e2m1 + E8M0 per 32 k): weight quantiser, decode image and the W4A16 16-row GEMV
+// w bf16 [N, K] -> (codes uint8 [N, K / 2], scales uint8 [N, K / 32]), row-major public format;
+// written into `codes` / `scales` when given (in-place refresh of captured buffers).
+std::vector<Tensor> quant_mxfp4(const Tensor& w, optional<Tensor> codes, optional<Tensor> scales) {
+  CHECK_CUDA(w); CHECK_BF16(w);
+  TORCH_CHECK(w.dim() == 2 && w.is_contiguous(), "quant_mxfp4: contiguous [N, K] weight expected");
+  CHECK_ALIGN16(w);
+  const int64_t N = w.size(0), K = w.size(1);
+  TORCH_CHECK(N > 0 && K > 0 && K % 32 == 0, "quant_mxfp4: needs K % 32 == 0");
+  Tensor q = (codes.has_value() && codes->defined()) ? *codes : at::empty({N, K / 2}, w.options().dtype(at::kByte));
+  Tensor s = (scales.has_value() && scales->defined()) ? *scales : at::empty({N, K / 32}, w.options().dtype(at::kByte));
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kByte && q.dim() == 2 && q.size(0) == N && q.size(1) == K / 2 &&
+                  q.is_contiguous() && q.device() == w.device(), "quant_mxfp4: codes must be contiguous uint8 [N, K / 2]");
+  TORCH_CHECK(s.is_cuda() && s.scalar_type() == at::kByte && s.dim() == 2 && s.size(0) == N && s.size(1) == K / 32 &&
+                  s.is_contiguous() && s.device() == w.device(), "quant_mxfp4: scales must be contiguous uint8 [N, K / 32]");
+  CHECK_ALIGN16(q);
+  check_rc(rt_quant_mxfp4(w.data_ptr(), q.data_ptr(), s.data_ptr(), N, K, cur_stream()), "quant_mxfp4");
+  return {q, s};
+}
+
+// Row-major MXFP4 (codes, scales) -> (code image, scale image) of the 16-row W4A16 kernel: same
+// shapes, permuted content (gemv_fp4 reads them).
+std::vector<Tensor> shuffle_decode_weight_fp4(const Tensor& codes, const Tensor& scales, optional<Tensor> img,
+                                              optional<Tensor> simg) {
+  CHECK_CUDA(codes); CHECK_CUDA(scales);
+  TORCH_CHECK(codes.scalar_type() == at::kByte && codes.dim() == 2 && codes.is_contiguous() &&
+                  scales.scalar_type() == at::kByte && scales.dim() == 2 && scales.is_contiguous() &&
+                  codes.device() == scales.device(),
+              "shuffle_decode_weight_fp4: contiguous uint8 codes [N, K / 2] and scales [N, K / 32] expected");
+  const int64_t N = codes.size(0), K = codes.size(1) * 2;
+  TORCH_CHECK(N > 0 && N % 16 == 0 && K > 0 && K % 256 == 0 && scales.size(0) == N && scales.size(1) == K / 32,
+              "shuffle_decode_weight_fp4: needs N % 16 == 0, K % 256 == 0 and scales [N, K / 32]");
+  Tensor o = (img.has_value() && img->defined()) ? *img : at::empty_like(codes);
+  Tensor so = (simg.has_value() && simg->defined()) ? *simg : at::empty_like(scales);
+  TORCH_CHECK(o.is_cuda() && o.sizes() == codes.sizes() && o.is_contiguous() && o.scalar_type() == at::kByte &&
+                  so.is_cuda() && so.sizes() == scales.sizes() && so.is_contiguous() && so.scalar_type() == at::kByte &&
+                  o.device() == codes.device() && so.device() == codes.device(),
+              "shuffle_decode_weight_fp4: bad out");
+  TORCH_CHECK(o.data_ptr() != codes.data_ptr() && so.data_ptr() != scales.data_ptr(),
+              "shuffle_decode_weight_fp4: out must not alias the source");
+  CHECK_ALIGN16(codes); CHECK_ALIGN16(o);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(so.data_ptr()) % 2 == 0, "shuffle_decode_weight_fp4: scale image alignment");
+  check_rc(rt_shuffle_decode_weight_fp4(codes.data_ptr(), scales.data_ptr(), o.data_ptr(), so.data_ptr(), N, K, cur_stream()),
+           "shuffle_decode_weight_fp4");
+  return {o, so};
+}
+
+// C = act(rstd(a) a W^T + bias) + R for a bf16 [M <= 16, K] and the MXFP4 image (img [N, K / 2],
+// simg [N, K / 32]) of W [N, K]; act 5 = SwiGLU over W = [gate; up] -> [M, N / 2].
+Tensor gemv_fp4(const Tensor& a, const Tensor& img, const Tensor& simg, const optional<Tensor>& bias, int64_t act,
+                bool out_f32, optional<Tensor> out, const optional<Tensor>& residual, double norm_eps) {
+  CHECK_CUDA(a); CHECK_CUDA(img); CHECK_CUDA(simg); CHECK_BF16(a); CHECK_ROWS(a); CHECK_ALIGN16(a);
+  TORCH_CHECK(img.scalar_type() == at::kByte && img.dim() == 2 && img.is_contiguous() &&
+                  simg.scalar_type() == at::kByte && simg.dim() == 2 && simg.is_contiguous(),
+              "gemv_fp4: contiguous uint8 images [N, K / 2] and [N, K / 32] expected");
+  TORCH_CHECK(img.device() == a.device() && simg.device() == a.device(), "gemv_fp4: operands on different devices");
+  const int64_t M = a.size(0), K = a.size(1), N = img.size(0);
+  const bool pair = act == 5;
+  TORCH_CHECK(M <= 16, "gemv_fp4: at most 16 rows");
+  TORCH_CHECK(K > 0 && K % 256 == 0 && N > 0 && N % (pair ? 64 : 16) == 0 && img.size(1) == K / 2 && simg.size(0) == N &&
+                  simg.size(1) == K / 32,
+              "gemv_fp4: needs K % 256 == 0, N % 16 == 0 (SwiGLU: N % 64 == 0), img [N, K / 2], simg [N, K / 32]");
+  TORCH_CHECK(act >= 0 && act <= 5, "gemv_fp4: unknown activation");
+  TORCH_CHECK(M <= 1 || a.stride(0) % 8 == 0, "gemv_fp4: row stride of a must be a multiple of 8");  // 16-B row loads
+  CHECK_ALIGN16(img);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(simg.data_ptr()) % 2 == 0, "gemv_fp4: scale image alignment");
+  if (bias.has_value() && bias->defined()) {
+    CHECK_CUDA(*bias); CHECK_BF16(*bias);
+    TORCH_CHECK(bias->numel() == N && bias->is_contiguous(), "gemv_fp4: bias [N]");
+  }
+  const int64_t Nout = pair ? N / 2 : N;
+  const auto odt = out_f32 ? at::kFloat : at::kBFloat16;
+  Tensor c = (out.has_value() && out->defined()) ? *out : at::empty({M, Nout}, a.options().dtype(odt));
+  TORCH_CHECK(c.is_cuda() && c.device() == a.device() && c.dim() == 2 && c.size(0) == M && c.size(1) == Nout &&
+                  c.stride(1) == 1 && c.scalar_type() == odt, "gemv_fp4: out");
+  if (M == 0) return c;
+  const bool has_res = residual.has_value() && residual->defined();
+  if (has_res) {
+    CHECK_CUDA(*residual); CHECK_BF16(*residual);
+    TORCH_CHECK(!pair, "gemv_fp4: no residual in SwiGLU pair mode");
+    TORCH_CHECK(residual->dim() == 2 && residual->size(0) == M && residual->size(1) == Nout && residual->stride(1) == 1,
+                "gemv_fp4: residual shape");
+  }
+  check_rc(rt_gemv_fp4(a.data_ptr(), M == 1 ? 0 : a.stride(0), img.data_ptr(), simg.data_ptr(), opt_ptr(bias), c.data_ptr(),
+                       c.stride(0), (int)M, (int)N, (int)K, (int)act, out_f32 ? 1 : 0,
+                       has_res ? residual->data_ptr() : nullptr, has_res ? residual->stride(0) : 0, (float)norm_eps,
+                       cur_stream()),
+           "gemv_fp4");
   return c;
 }
 
@@ -1416,6 +1512,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("shuffle_decode_weight_fp8", &shuffle_decode_weight_fp8,
         "fp8 W [N, K] -> tile-ordered W8A16 decode image (gemm_fp8 w_shuffled=True)", py::arg("q"),
         py::arg("out") = py::none());
+  m.def("quant_mxfp4", &quant_mxfp4, "bf16 W [N, K] -> MXFP4 (codes uint8 [N, K/2], E8M0 scales uint8 [N, K/32])",
+        py::arg("w"), py::arg("codes") = py::none(), py::arg("scales") = py::none());
+  m.def("shuffle_decode_weight_fp4", &shuffle_decode_weight_fp4,
+        "row-major MXFP4 (codes, scales) -> (code image, scale image) of the W4A16 16-row kernel", py::arg("codes"),
+        py::arg("scales"), py::arg("img") = py::none(), py::arg("simg") = py::none());
+  m.def("gemv_fp4", &gemv_fp4, "W4A16 decode GEMV (M <= 16) on the MXFP4 image", py::arg("a"), py::arg("img"),
+        py::arg("simg"), py::arg("bias") = py::none(), py::arg("act") = 0, py::arg("out_f32") = false,
+        py::arg("out") = py::none(), py::arg("residual") = py::none(), py::arg("norm_eps") = 0.0);
   m.def("get_tuning", &get_tuning, "the launchers' kernel-selection knobs (rt::Tuning) as a dict");
   m.def("set_tuning", &set_tuning, "update rt::Tuning fields from a dict (unknown keys raise)");
   m.def("attn_decode_fused", &attn_decode_fused, "RoPE + KV append + split-K decode attention + combine",

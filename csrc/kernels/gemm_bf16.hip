@@ -381,6 +381,59 @@ static int gemv_cus() {
   return n;
 }
 
+// Tail of the 16-row no-split kernels (bf16 / fp8 / MXFP4 images): the waves' partial sums meet in
+// LDS and are summed in wave order, then in-GEMM RMS-norm scaling, per-column scale (W8), bias,
+// activation or the SwiGLU gate / up pair, residual, bf16 / fp32 store.
+template <bool OUT_F32, bool PAIR, bool W8, int NW>
+__device__ __forceinline__ void gemv16_finish(const GemmArgs& p, const f32x4& acc, const f32x4& accu, float sq,
+                                              float (&red)[NW][16][PAIR ? 33 : 17], float (&rsq)[NW][16], int grp) {
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int frow = lane & 15, g = lane >> 4;
+  const bool normed = p.norm_eps > 0.f;
+  // acc[r] of lane (frow, g) = C[row 4 g + r][16 grp + frow] over this wave's k range; the X row
+  // sum of squares of row frow is spread over its 4 g lanes
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) {
+    red[wid][4 * g + rr][frow] = acc[rr];
+    if constexpr (PAIR) red[wid][4 * g + rr][16 + frow] = accu[rr];
+  }
+  if (normed) {
+    float t = sq;
+    t += __shfl_xor(t, 16, 64);
+    t += __shfl_xor(t, 32, 64);
+    if (g == 0) rsq[wid][frow] = t;
+  }
+  __syncthreads();
+  const int row = tid >> 4, ci = tid & 15;
+  if (row < p.M) {
+    const int col = grp * 16 + ci;
+    // wave partials summed in wave order (NW = 4: the association of the original four-term sum)
+    float ss = 0.f, yy = 0.f, uu = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      ss += rsq[w][row];
+      yy += red[w][row][ci];
+      if constexpr (PAIR) uu += red[w][row][16 + ci];
+    }
+    const float rs = normed ? rsqrtf(ss / (float)p.K + p.norm_eps) : 1.f;
+    float y = yy * rs;
+    if constexpr (PAIR) {
+      const int F = p.N / 2;
+      float up = uu * rs;
+      if constexpr (W8) { y *= p.sb[col]; up *= p.sb[F + col]; }
+      if (p.bias) { y += bf2f(p.bias[col]); up += bf2f(p.bias[F + col]); }
+      y = y / (1.f + __expf(-y)) * up;
+    } else {
+      if constexpr (W8) y *= p.sb[col];
+      if (p.bias) y += bf2f(p.bias[col]);
+      y = apply_act(y, p.act);
+      if (p.R) y += bf2f(p.R[(long)row * p.ldr + col]);
+    }
+    if constexpr (OUT_F32) ((float*)p.C)[(long)row * p.ldc + col] = y;
+    else ((bf16_t*)p.C)[(long)row * p.ldc + col] = f2bf(y);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Decode GEMV (M <= 16) without split-K: one workgroup per 16 weight rows of a tile-ordered image
 // ---------------------------------------------------------------------------------------------
@@ -494,48 +547,110 @@ __global__ __launch_bounds__(64 * NW) void gemv16_kernel(GemmArgs p) {
 #pragma unroll
   for (int i = 0; i < DEPTH - 1; ++i)
     if (c + i < c_end) mma(r[i]);
-  // acc[r] of lane (frow, g) = C[row 4 g + r][16 grp + frow] over this wave's k range; the X row
-  // sum of squares of row frow is spread over its 4 g lanes
-#pragma unroll
-  for (int rr = 0; rr < 4; ++rr) {
-    red[wid][4 * g + rr][frow] = acc[rr];
-    if constexpr (PAIR) red[wid][4 * g + rr][16 + frow] = accu[rr];
-  }
-  if (normed) {
-    float t = sq;
-    t += __shfl_xor(t, 16, 64);
-    t += __shfl_xor(t, 32, 64);
-    if (g == 0) rsq[wid][frow] = t;
-  }
-  __syncthreads();
-  const int row = tid >> 4, ci = tid & 15;
-  if (row < p.M) {
-    const int col = grp * 16 + ci;
-    // wave partials summed in wave order (NW = 4: the association of the original four-term sum)
-    float ss = 0.f, yy = 0.f, uu = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      ss += rsq[w][row];
-      yy += red[w][row][ci];
-      if constexpr (PAIR) uu += red[w][row][16 + ci];
-    }
-    const float rs = normed ? rsqrtf(ss / (float)p.K + p.norm_eps) : 1.f;
-    float y = yy * rs;
+  gemv16_finish<OUT_F32, PAIR, W8, NW>(p, acc, accu, sq, red, rsq, grp);
+}
+
+// MXFP4 (W4A16, model.fp4_decode) form of the 16-row kernel: OCP MX weights — e2m1 codes, two per
+// byte, one E8M0 scale byte per 32 consecutive k of a row — a quarter of the bf16 weight bytes.
+// Image (shuffle_decode_weight_fp4): per 16-row group G, 2-KiB chunks of 256 k; load h = 0, 1 of
+// lane l = 16 g + r holds the 16 code bytes of row 16 G + r at k [256 c + 128 h + 32 g, +32): one
+// whole MX block, so one scale byte per load. Dword j of the load is k [.. + 8 j, +8) in order
+// (element 2 i in the low nibble of byte i), widened by the hardware e2m1 -> bf16 conversion with
+// the block's scale applied (exact: an MXFP4 weight is a bf16 number) into the B fragment of MFMA
+// j; the X fragment of MFMA j is the lane's 16 B at the same k, so both operands agree on the
+// k-slot permutation and the MFMA sums the right products. Scale image: one 16-bit word per (chunk,
+// lane) = the scale bytes of loads h = 0 (low) and 1 (high), 128 contiguous bytes per wave and
+// chunk, loaded in the same pipeline stage as the codes. B points to the code image; the epilogue
+// (gemv16_finish) and the wave-order sum of the partials are those of the bf16 kernel.
+__device__ __forceinline__ bf16x8 fp4x8_to_bf16(unsigned v, float scale) {
+  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+  const bf16x2_t a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 0);
+  const bf16x2_t b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 1);
+  const bf16x2_t c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 2);
+  const bf16x2_t d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 3);
+  return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
+// E8M0 byte s -> 2^(s - 127) as a float (s = 0 is the fp32 denormal 2^-127)
+__device__ __forceinline__ float e8m0_to_float(unsigned s) {
+  return __uint_as_float(s ? (s << 23) : 0x00400000u);
+}
+
+template <bool OUT_F32, int DEPTH, bool PAIR, int NW>
+__global__ __launch_bounds__(64 * NW) void gemv16_fp4_kernel(GemmArgs p, const unsigned short* __restrict__ simg) {
+  __shared__ float red[NW][16][PAIR ? 33 : 17];
+  __shared__ float rsq[NW][16];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int frow = lane & 15, g = lane >> 4;
+  const int grp = blockIdx.x;  // 16-row group (of the gate rows when PAIR)
+  const int nc = p.K / 256;
+  const int c_begin = wid * nc / NW, c_end = (wid + 1) * nc / NW;
+  const long ugrp = PAIR ? (long)(p.N / 32) + grp : grp;
+  const char* wbase = (const char*)p.B + (long)grp * nc * 2048 + lane * 16;
+  const char* ubase = (const char*)p.B + ugrp * nc * 2048 + lane * 16;
+  const unsigned short* sbase = simg + (long)grp * nc * 64 + lane;
+  const unsigned short* subase = simg + ugrp * nc * 64 + lane;
+  const bf16_t* xrow = p.A + (long)min(frow, p.M - 1) * p.lda + g * 32;
+  struct Regs { uint4 w0, w1, u0, u1, x[8]; unsigned sw, su; };
+  auto ld = [&](Regs& r, int c) {
+    r.w0 = load_nt16(wbase + (long)c * 2048);
+    r.w1 = load_nt16(wbase + (long)c * 2048 + 1024);
+    r.sw = __builtin_nontemporal_load(sbase + (long)c * 64);
     if constexpr (PAIR) {
-      const int F = p.N / 2;
-      float up = uu * rs;
-      if constexpr (W8) { y *= p.sb[col]; up *= p.sb[F + col]; }
-      if (p.bias) { y += bf2f(p.bias[col]); up += bf2f(p.bias[F + col]); }
-      y = y / (1.f + __expf(-y)) * up;
-    } else {
-      if constexpr (W8) y *= p.sb[col];
-      if (p.bias) y += bf2f(p.bias[col]);
-      y = apply_act(y, p.act);
-      if (p.R) y += bf2f(p.R[(long)row * p.ldr + col]);
+      r.u0 = load_nt16(ubase + (long)c * 2048);
+      r.u1 = load_nt16(ubase + (long)c * 2048 + 1024);
+      r.su = __builtin_nontemporal_load(subase + (long)c * 64);
     }
-    if constexpr (OUT_F32) ((float*)p.C)[(long)row * p.ldc + col] = y;
-    else ((bf16_t*)p.C)[(long)row * p.ldc + col] = f2bf(y);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {  // k [256 c + 128 h + 32 g + 8 j, +8), h = 0, 1
+      r.x[j] = *(const uint4*)(xrow + c * 256 + 8 * j);
+      r.x[4 + j] = *(const uint4*)(xrow + c * 256 + 128 + 8 * j);
+    }
+  };
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f}, accu = acc;
+  float sq = 0.f;
+  const bool normed = p.norm_eps > 0.f;
+  auto mma = [&](const Regs& r) {
+    const unsigned w[8] = {r.w0.x, r.w0.y, r.w0.z, r.w0.w, r.w1.x, r.w1.y, r.w1.z, r.w1.w};
+    const float sw[2] = {e8m0_to_float(r.sw & 0xffu), e8m0_to_float(r.sw >> 8)};
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, r.x[j]), fp4x8_to_bf16(w[j], sw[j >> 2]), acc,
+                                                    0, 0, 0);
+    if constexpr (PAIR) {
+      const unsigned u[8] = {r.u0.x, r.u0.y, r.u0.z, r.u0.w, r.u1.x, r.u1.y, r.u1.z, r.u1.w};
+      const float su[2] = {e8m0_to_float(r.su & 0xffu), e8m0_to_float(r.su >> 8)};
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        accu = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, r.x[j]), fp4x8_to_bf16(u[j], su[j >> 2]),
+                                                       accu, 0, 0, 0);
+    }
+    if (normed) {
+      float f[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        unpack8(r.x[j], f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) sq += f[e] * f[e];
+      }
+    }
+  };
+  Regs r[DEPTH];
+#pragma unroll
+  for (int i = 0; i < DEPTH - 1; ++i)
+    if (c_begin + i < c_end) ld(r[i], c_begin + i);
+  int c = c_begin;
+  for (; c + DEPTH <= c_end; c += DEPTH) {
+#pragma unroll
+    for (int i = 0; i < DEPTH; ++i) {
+      if (c + i + DEPTH - 1 < c_end) ld(r[(i + DEPTH - 1) % DEPTH], c + i + DEPTH - 1);
+      mma(r[i]);
+    }
   }
+#pragma unroll
+  for (int i = 0; i < DEPTH - 1; ++i)
+    if (c + i < c_end) mma(r[i]);
+  gemv16_finish<OUT_F32, PAIR, false, NW>(p, acc, accu, sq, red, rsq, grp);
 }
 
 // Shared tail of the M <= 64 kernels: split-K hand-off (write-through slabs + ticket, last arriver
@@ -1364,6 +1479,116 @@ extern "C" int rt_shuffle_decode_weight_fp8(const void* src, void* dst, long N, 
   const int blocks = (int)std::min<long>((total + 255) / 256, 8192);
   hipLaunchKernelGGL(shuffle_decode_weight_fp8_kernel, dim3(blocks), dim3(256), 0, stream, (const uint4*)src,
                      (uint4*)dst, N, K);
+  RT_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// MXFP4 (OCP MX e2m1 + E8M0) weight quantiser, decode image and the W4A16 16-row GEMV launch
+// ---------------------------------------------------------------------------------------------
+// Public format (ops/fp4.py is the CPU oracle; the codes and scales here are bitwise its): blocks of
+// 32 consecutive k of a row; scale byte s = e + 127 with e = (exponent field of amax) - 127 - 2
+// clamped to [-127, 127], e = 0 for an all-zero block; elements x * 2^-e (exact), magnitude
+// rounded to nearest-even on {0, .5, 1, 1.5, 2, 3, 4, 6} (saturating at 6) by threshold compares,
+// the sign bit is the input's. codes [N, K / 2]: element 2 i in the low nibble of byte i.
+// Four lanes per block, 8 elements (one 16-B load, one dword of codes) each; amax by shuffles.
+__global__ __launch_bounds__(256) void quant_mxfp4_kernel(const uint4* __restrict__ src, uint32_t* __restrict__ codes,
+                                                          uint8_t* __restrict__ scales, long total) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const uint4 v = src[i];
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    float f[8];
+    unpack8(v, f);
+    float amax = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(f[e]));
+    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+    amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+    int ex = 0;
+    if (amax != 0.f) ex = min(max((int)((__float_as_uint(amax) >> 23) & 0xffu) - 129, -127), 127);
+    const float inv = __uint_as_float((uint32_t)(127 - ex) << 23);  // 2^-ex, a normal float for every ex
+    uint32_t out = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float a = fabsf(f[e]) * inv;
+      const uint32_t code = (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) + (uint32_t)(a >= 1.75f) +
+                            (uint32_t)(a > 2.5f) + (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.f);
+      const uint32_t sign = (w[e >> 1] >> ((e & 1) ? 31 : 15)) & 1u;
+      out |= (code | (sign << 3)) << (4 * e);
+    }
+    codes[i] = out;
+    if ((i & 3) == 0) scales[i >> 2] = (uint8_t)(ex + 127);
+  }
+}
+
+extern "C" int rt_quant_mxfp4(const void* w, void* codes, void* scales, long N, long K, hipStream_t stream) {
+  if (N <= 0 || K <= 0 || K % 32) return -1;
+  const long total = N * K / 8;
+  const int blocks = (int)std::min<long>((total + 255) / 256, 8192);
+  hipLaunchKernelGGL(quant_mxfp4_kernel, dim3(blocks), dim3(256), 0, stream, (const uint4*)w, (uint32_t*)codes,
+                     (uint8_t*)scales, total);
+  RT_LAUNCH_CHECK();
+  return 0;
+}
+
+// Row-major MXFP4 codes [N, K / 2] + scales [N, K / 32] -> the image of gemv16_fp4_kernel (layout
+// there). Code image: 16-B unit i = lane l = i & 63 of load h = (i >> 6) & 1 of tile i >> 7 =
+// (G, c): row 16 G + (l & 15), MX block 8 c + 4 h + (l >> 4). Scale image: 16-bit word i = lane
+// l = i & 63 of tile i >> 6: the scale bytes of that row's blocks 8 c + (l >> 4) (low byte) and
+// + 4 (high byte). One thread per 16 B of codes, then one per scale word.
+__global__ __launch_bounds__(256) void shuffle_decode_weight_fp4_kernel(const uint4* __restrict__ codes,
+                                                                        const uint8_t* __restrict__ scales,
+                                                                        uint4* __restrict__ img,
+                                                                        unsigned short* __restrict__ simg, long N, long K) {
+  const long nc = K / 256, nb = K / 32;
+  const long total = N * nb;  // 16-B units of codes = MX blocks
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long l = i & 63, h = (i >> 6) & 1, tile = i >> 7;
+    const long G = tile / nc, c = tile % nc;
+    img[i] = codes[(G * 16 + (l & 15)) * nb + c * 8 + h * 4 + (l >> 4)];
+  }
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total / 2; i += (long)gridDim.x * 256) {
+    const long l = i & 63, tile = i >> 6;
+    const long G = tile / nc, c = tile % nc;
+    const uint8_t* s = scales + (G * 16 + (l & 15)) * nb + c * 8 + (l >> 4);
+    simg[i] = (unsigned short)((unsigned)s[0] | ((unsigned)s[4] << 8));
+  }
+}
+
+extern "C" int rt_shuffle_decode_weight_fp4(const void* codes, const void* scales, void* img, void* simg, long N, long K,
+                                            hipStream_t stream) {
+  if (N <= 0 || K <= 0 || N % 16 || K % 256) return -1;
+  const long total = N * K / 32;
+  const int blocks = (int)std::min<long>((total + 255) / 256, 8192);
+  hipLaunchKernelGGL(shuffle_decode_weight_fp4_kernel, dim3(blocks), dim3(256), 0, stream, (const uint4*)codes,
+                     (const uint8_t*)scales, (uint4*)img, (unsigned short*)simg, N, K);
+  RT_LAUNCH_CHECK();
+  return 0;
+}
+
+// C[M, N] = epilogue(X[M, K] · W^T), M <= 16, W the MXFP4 image above (N = weight rows, 2 F for
+// SwiGLU). The variant depends on the shape alone, never on M, so a row's arithmetic is the same in
+// a 1-row decode step and a 16-row verify step: 8 waves per row group when the grid has at most one
+// workgroup per CU (the rule of the bf16 kernel), else 4; the SwiGLU pair form runs 4.
+extern "C" int rt_gemv_fp4(const void* A, long lda, const void* img, const void* simg, const void* bias, void* C, long ldc,
+                           int M, int N, int K, int act, int out_f32, const void* R, long ldr, float norm_eps,
+                           hipStream_t stream) {
+  GemmArgs p;
+  p.A = (const bf16_t*)A; p.lda = lda; p.B = (const bf16_t*)img; p.ldb = 0;
+  p.U = nullptr; p.ldu = 0; p.UB = nullptr; p.ldub = 0; p.Rp = 0;
+  p.bias = (const bf16_t*)bias; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.act = act;
+  p.sa = nullptr; p.sb = nullptr;
+  p.R = (const bf16_t*)R; p.ldr = ldr; p.norm_eps = norm_eps; p.wshuf = 1;
+  if (M <= 0 || N <= 0) return 0;
+  const bool pair = act == ACT_SWIGLU;
+  if (M > 16 || K <= 0 || K % 256 || N % 16 || (pair && N % 64) || lda % 8) return -4;
+  dim3 grid(pair ? N / 32 : N / 16);
+  const unsigned short* s = (const unsigned short*)simg;
+#define G4(P, W)                                                                                              \
+  if (out_f32) hipLaunchKernelGGL((gemv16_fp4_kernel<true, 3, P, W>), grid, dim3(64 * W), 0, stream, p, s); \
+  else hipLaunchKernelGGL((gemv16_fp4_kernel<false, 3, P, W>), grid, dim3(64 * W), 0, stream, p, s);
+  if (pair) { G4(true, 4) } else if ((int)grid.x <= gemv_cus()) { G4(false, 8) } else { G4(false, 4) }
+#undef G4
   RT_LAUNCH_CHECK();
   return 0;
 }

@@ -131,6 +131,15 @@ def _apply_fp8(cfg, policy):
     return policy
 
 
+def apply_fp4(cfg, policy):
+    """``model.fp4_decode``: MXFP4 decode images for RAG answers at up to 16 rows."""
+    if policy is not None and getattr(cfg.model, "fp4_decode", False):
+        if not hasattr(policy, "set_fp4_decode"):
+            raise ValueError("model.fp4_decode: the policy has no MXFP4 decode path")
+        policy.set_fp4_decode(True)
+    return policy
+
+
 def cmd_rag(cfg, args):
     from .generation import SamplingParams
     from .rag import RagPipeline
@@ -138,6 +147,7 @@ def cmd_rag(cfg, args):
     di = _device()
     st = build_stack(cfg, di.device)
     _apply_fp8(cfg, st["policy"])
+    apply_fp4(cfg, st["policy"])
     sp = SamplingParams(max_new_tokens=cfg.ppo.max_new_tokens, temperature=cfg.eval.temperature,
                         do_sample=cfg.eval.do_sample, top_k=cfg.eval.top_k, lookup_tokens=cfg.eval.lookup_tokens,
                         lookup_ngram=cfg.eval.lookup_ngram)
@@ -302,6 +312,7 @@ def cmd_eval(cfg, args):
 
     di = _device()
     st = build_stack(cfg, di.device)
+    apply_fp4(cfg, st["policy"])
     recs = _held_out_records(cfg, st, min(cfg.data.n_queries, 64))
     ev = Evaluator(RewardModel(st["encoder"], cfg.reward), cfg.eval)
     base, tok = st["policy"], st["tokenizer"]

@@ -35,6 +35,10 @@ class ModelSection:
     # with fp8: the frozen base product of LoRA training forwards on the fp8 MFMA too (adapter
     # term and backward stay bf16; loss parity checked in tests/test_kernels_gpu.py)
     fp8_train: bool = False
+    # MXFP4 (W4A16) weight images of the fused decode layer's four projections for decode / verify
+    # steps of <= 16 rows (RAG answers): a quarter of the bf16 weight bytes per token at ~11 %
+    # relative rms weight error. Not with fp8; Llama / Mistral only
+    fp4_decode: bool = False
 
 
 @dataclass

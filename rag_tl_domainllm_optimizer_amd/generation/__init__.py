@@ -94,6 +94,11 @@ class _GraphSet:
         self.cur = None
 
 
+def _fp4_decode_on(model) -> bool:
+    layers = getattr(model, "layers", None)
+    return bool(layers) and getattr(layers[0], "fp4_decode", False)
+
+
 class KVCache:
     """Static K/V cache [L, B, Hkv, Smax, D]. ``fp8``: e4m3fn bytes (K rows k-permuted) plus one
     fp32 scale per (layer, row, kv head, slot) in ``ks`` / ``vs`` [L, B, Hkv, SmaxP] (SmaxP = Smax
@@ -384,6 +389,9 @@ class Generator:
             if max_b is not None and self._nb * (K + 1) > max_b:
                 raise ValueError(f"prompt-lookup decoding: {self._nb} rows x {K + 1} positions exceed the fused "
                                  f"decode layer's limit of {max_b} rows")
+        if K > 0 and _fp4_decode_on(self.model) and self._nb * (K + 1) > 16:
+            raise ValueError(f"prompt-lookup decoding: {self._nb} rows x {K + 1} positions exceed the 16 rows of the "
+                             f"MXFP4 decode kernels (model.fp4_decode)")
         if hasattr(self.model, "refresh_decode_weights"):
             # folded / tile-ordered / fp8 images of graph replays; a verify step runs rows * (K + 1) rows
             self.model.refresh_decode_weights(self._nb * (K + 1))
@@ -421,6 +429,8 @@ class Generator:
         key = (T, params.inv_temp, params.top_k, params.top_p, params.greedy, params.seed, tuple(eos_list), pad_id,
                self._nb)
         step = self._step
+        if _fp4_decode_on(self.model):
+            key = key + ("fp4",)  # the captured step of the other setting streams other weight images
         if self._lk is not None:
             # a verify step is its own graph per (K, n-gram length); plain keys are unchanged
             key = key + ("lookup", params.lookup_tokens, params.lookup_ngram)
@@ -653,6 +663,9 @@ class ContinuousBatcher:
     def __init__(self, gen: Generator, params: SamplingParams, pad_id: int = 0, eos_ids: Sequence[int] = ()):
         if params.lookup_tokens > 0:
             raise NotImplementedError("prompt-lookup decoding is not supported with continuous batching")
+        if _fp4_decode_on(gen.model) and gen.max_batch > 16:
+            raise ValueError(f"continuous batching with MXFP4 decode (model.fp4_decode): max_batch {gen.max_batch} "
+                             f"exceeds the 16 rows of the MXFP4 decode kernels")
         self.gen, self.params, self.pad_id = gen, params, pad_id
         g = gen
         g._lk = None

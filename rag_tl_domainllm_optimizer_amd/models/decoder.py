@@ -59,6 +59,9 @@ class DecoderLayer(nn.Module):
         self.fp8_enabled = False
         self.fp8_train = False  # W8A8 frozen-base product in LoRA training forwards (config 5)
         self._fp8: Dict[str, ops.Fp8Cache] = {}
+        # MXFP4 decode images of the four fused-decode projections (CausalLM.set_fp4_decode)
+        self.fp4_decode = False
+        self._fp4: Dict[str, ops.Fp4Cache] = {}
         # norm-folded weights of the fused decode path (Llama/Mistral)
         self._fold: Dict[str, ops.FoldCache] = {}
         # tile-ordered images of the split-K decode projections (qkv, o, down) for batch <= 16
@@ -90,6 +93,21 @@ class DecoderLayer(nn.Module):
             return None, None
         return None, self._shufc.setdefault(shufname, ops.ShufCache())
 
+    def _f4(self, name: str, w: torch.Tensor, m: int, act: int = 0):
+        """Fp4Cache of one decode projection (``set_fp4_decode``) for a step of ``m`` rows, or None:
+        steps above 16 rows and projections ``fp4_projection`` leaves on bf16 keep the bf16 path."""
+        if not self.fp4_decode or m > 16 or not fp4_projection(w, act):
+            return None
+        return self._fp4.setdefault(name, ops.Fp4Cache())
+
+    def _dec(self, f8name: str, name: str, w: torch.Tensor, m: int, act: int = 0):
+        """Weight-image arguments of one decode projection's ``ops.gemm_decode`` call."""
+        f4 = self._f4(name, w, m, act)
+        if f4 is not None:
+            return {"fp4": f4}
+        f8, sh = self._dec_caches(f8name, name, w, m)
+        return {"fp8": f8, "shuf": sh}
+
     # ---------------------------------------------------------------- fused decode step (M <= 64)
     def _w_eff(self, wname: str, gname: str):
         w = getattr(self, wname)
@@ -101,9 +119,10 @@ class DecoderLayer(nn.Module):
         return g.merged_weight(w)
 
     @torch.no_grad()
-    def refresh_decode_weights(self):
+    def refresh_decode_weights(self, fp4: bool = True):
         """Bring the merged / folded / fp8 decode weights up to date eagerly (graph replays of a
-        captured decode step only read them)."""
+        captured decode step only read them). ``fp4`` False leaves the MXFP4 images alone (a step
+        above 16 rows does not read them)."""
         if self.cfg.arch == "opt":
             return
         wq = self._fold.setdefault("qkv", ops.FoldCache()).get(self._w_eff("qkv_w", "qkv"), self.ln1_w)
@@ -116,6 +135,11 @@ class DecoderLayer(nn.Module):
         for name, w in (("qkv", wq), ("o", wo), ("gate_up", wgu), ("down", wd)):
             if name in self._shufc:  # images exist once a batch <= 16 decode ran
                 self._shufc[name].get(w)
+        if self.fp4_decode and fp4:
+            for name, w, act in (("qkv", wq, 0), ("o", wo, 0), ("gate_up", wgu, ops.ACT_SWIGLU), ("down", wd, 0)):
+                c = self._f4(name, w, 1, act)
+                if c is not None:
+                    c.image(w) if ops.on_gpu(w) else c.get(w)
 
     def decode_fused(self, h, attend):
         """One Llama/Mistral layer of a decode step in four kernels: [RMSNorm folded into the qkv
@@ -125,17 +149,15 @@ class DecoderLayer(nn.Module):
         eps = cfg.norm_eps
         m = h.shape[0]
         wq = self._fold.setdefault("qkv", ops.FoldCache()).get(self._w_eff("qkv_w", "qkv"), self.ln1_w)
-        f8, sh = self._dec_caches("qkv_folded", "qkv", wq, m)
-        qkv = ops.gemm_decode(h, wq, norm_eps=eps, fp8=f8, shuf=sh)
+        # weight images per projection (_dec): fp8 / tile-ordered bf16, or MXFP4 under set_fp4_decode
+        qkv = ops.gemm_decode(h, wq, norm_eps=eps, **self._dec("qkv_folded", "qkv", wq, m))
         wo = self._w_eff("o_w", "o")
-        f8, sh = self._dec_caches("o", "o", wo, m)
-        h = ops.gemm_decode(attend(qkv), wo, residual=h, fp8=f8, shuf=sh)
+        h = ops.gemm_decode(attend(qkv), wo, residual=h, **self._dec("o", "o", wo, m))
         wgu = self._fold.setdefault("gate_up", ops.FoldCache()).get(self._w_eff("gate_up_w", "gate_up"), self.ln2_w)
-        f8, sh = self._dec_caches("gate_up_folded", "gate_up", wgu, m)
-        f = ops.gemm_decode(h, wgu, act=ops.ACT_SWIGLU, norm_eps=eps, fp8=f8, shuf=sh)
+        f = ops.gemm_decode(h, wgu, act=ops.ACT_SWIGLU, norm_eps=eps,
+                            **self._dec("gate_up_folded", "gate_up", wgu, m, ops.ACT_SWIGLU))
         wd = self._w_eff("down_w", "down")
-        f8, sh = self._dec_caches("down", "down", wd, m)
-        return ops.gemm_decode(f, wd, residual=h, fp8=f8, shuf=sh)
+        return ops.gemm_decode(f, wd, residual=h, **self._dec("down", "down", wd, m))
 
     def attn_in(self, x, residual, defer: bool = False):
         """``defer`` (no-grad decode, batch > 64): the qkv GEMM may return unreduced split-K
@@ -398,7 +420,8 @@ class CausalLM(nn.Module):
         x = self.embed_tokens(tokens, pos)
         fp8 = bool(self.layers) and self.layers[0].fp8_enabled
         max_b = self.fused_decode_max_batch_fp8 if fp8 else self.fused_decode_max_batch
-        if (self.fused_decode and cfg.arch != "opt" and x.is_cuda and x.shape[0] <= max_b
+        fp4 = bool(self.layers) and self.layers[0].fp4_decode  # its CPU twin runs the fused layer too
+        if (self.fused_decode and cfg.arch != "opt" and (x.is_cuda or fp4) and x.shape[0] <= max_b
                 and not torch.is_grad_enabled()):
             h = x
             kv8 = getattr(cache, "fp8", False)
@@ -443,6 +466,10 @@ class CausalLM(nn.Module):
         if tokens.is_cuda and B * G > max_b:
             raise ValueError(f"decode_verify: {B} rows x {G} positions exceed the fused decode layer's "
                              f"limit of {max_b} rows")
+        fp4 = bool(self.layers) and self.layers[0].fp4_decode
+        if fp4 and B * G > 16:
+            raise ValueError(f"decode_verify: {B} rows x {G} positions exceed the 16 rows of the MXFP4 decode "
+                             f"kernels (model.fp4_decode)")
         cos, sin = self.rope(tokens.device)
         x = self.embed_tokens(tokens.reshape(-1), None)
 
@@ -450,7 +477,7 @@ class CausalLM(nn.Module):
             return ops.verify_step_attention(qkv, cache.k[li], cache.v[li], slot0, attn_len0, cfg.num_heads, G,
                                              pos0, cos, sin, kv_start, cfg.sliding_window, workspace=workspace)
 
-        if self.fused_decode and x.is_cuda and not torch.is_grad_enabled():
+        if self.fused_decode and (x.is_cuda or fp4) and not torch.is_grad_enabled():
             h = x
             for li, layer in enumerate(self.layers):
                 h = layer.decode_fused(h, lambda qkv, li=li: attend_layer(qkv, li))
@@ -501,7 +528,7 @@ class CausalLM(nn.Module):
                 return
         if self.fused_decode:
             for layer in self.layers:
-                layer.refresh_decode_weights()
+                layer.refresh_decode_weights(fp4=batch is None or batch <= 16)
         if self._head_shuf is not None:
             self._head_shuf.get(self.head_weight)
 
@@ -511,10 +538,29 @@ class CausalLM(nn.Module):
         base product of LoRA training forwards runs W8A8 as well (the adapter term and every
         backward GEMM stay bf16); None keeps the current setting. Returns the previous ``on``."""
         prev = any(layer.fp8_enabled for layer in self.layers)
+        if on and any(layer.fp4_decode for layer in self.layers):
+            raise ValueError("set_fp8: MXFP4 decode (set_fp4_decode) is on; the two weight formats do not combine")
         for layer in self.layers:
             layer.fp8_enabled = on
             if train is not None:
                 layer.fp8_train = bool(train) and on
+        return prev
+
+    def set_fp4_decode(self, on: bool = True):
+        """MXFP4 (W4A16) images of the four fused-decode projections of every Llama / Mistral layer
+        for decode and verify steps of at most 16 rows: a quarter of the bf16 weight bytes per
+        token, quantised after LoRA merge and norm fold. Prefill, steps above 16 rows, scoring,
+        training, the LM head and the embeddings keep the bf16 weights. An opt-in latency /
+        quality trade (~11 % relative rms weight error, docs/DESIGN.md). Returns the previous
+        setting."""
+        prev = any(layer.fp4_decode for layer in self.layers)
+        if on:
+            if self.cfg.arch == "opt":
+                raise ValueError("set_fp4_decode: learned-position (opt) models have no fused decode layer")
+            if any(layer.fp8_enabled for layer in self.layers):
+                raise ValueError("set_fp4_decode: fp8 weights (set_fp8) are on; the two weight formats do not combine")
+        for layer in self.layers:
+            layer.fp4_decode = bool(on)  # the images stay: a captured step may still read them
         return prev
 
     def refresh_lora(self):
@@ -548,6 +594,15 @@ def packed_index(lo, hi, L: int, device):
 def pack_enabled() -> bool:
     """Varlen packing of training / scoring / prefill forwards (RAGTL_PACK=0 turns it off)."""
     return os.environ.get("RAGTL_PACK", "1") != "0"
+
+
+def fp4_projection(w: torch.Tensor, act: int = 0) -> bool:
+    """Whether a decode projection runs on its MXFP4 image under ``set_fp4_decode``: a choice by
+    shape only, never by the step's rows, so a 1-row decode step and a 16-row verify step do the
+    same arithmetic per row. Measured on Mistral-7B (docs/DESIGN.md "MXFP4 weight-only decode",
+    profiles/r9/fp4_decode.log): qkv, o, gate_up and down are all faster on the image at M = 1
+    (0.68x / 0.59x / 0.43x / 0.54x the bf16 GEMV) and at M = 16, so every supported shape takes it."""
+    return ops.fp4_supported(w, act)
 
 
 def shuffle_enabled(m: int) -> bool:

@@ -16,4 +16,5 @@ from .misc import (embedding, gae, ivf_scan, ppo_advantages, pool_normalize, ppo
                    swiglu, token_logprobs, topk, lookup_accept, lookup_draft)
 from .optim import FlatParams, FusedAdamW, MixedFlatParams, flat_params  # noqa: F401
 from .fp8 import Fp8Cache, dequantize_fp8, gemm_fp8, quantize_fp8  # noqa: F401
+from .fp4 import Fp4Cache, dequantize_mxfp4, fp4_supported, quantize_mxfp4  # noqa: F401
 from . import reference  # noqa: F401

@@ -853,12 +853,23 @@ def linear_deferred(x: torch.Tensor, w: torch.Tensor, bias=None, lora: Optional[
 
 
 def gemm_decode(x: torch.Tensor, w: torch.Tensor, act: int = 0, residual=None, norm_eps: float = 0.0, fp8=None,
-                shuf=None):
+                shuf=None, fp4=None):
     """Decode-step GEMM (M <= 64) with the fused prologue/epilogue of the skinny kernels:
     ``C = act(rstd(x) * x w^T) + residual`` where ``rstd`` (``norm_eps > 0``) is the RMS-norm of
     each input row computed inside the GEMM (the norm weight must already be folded into ``w``)
     and ``act`` may be ACT_SWIGLU (w = [gate; up]). ``fp8`` (Fp8Cache) streams e4m3fn weights;
-    ``shuf`` (ShufCache, M <= 16) streams the tile-ordered image of ``w`` instead."""
+    ``shuf`` (ShufCache, M <= 16) streams the tile-ordered image of ``w`` instead. ``fp4``
+    (Fp4Cache): at M <= 16 on a weight ``fp4_supported`` accepts, the MXFP4 image of ``w`` (W4A16
+    16-row kernel on the GPU, the eager oracle over ``dequantize_mxfp4`` on the CPU); any other
+    case takes the path below on the bf16 weight."""
+    if fp4 is not None and x.shape[0] <= 16:
+        from .fp4 import dequantize_mxfp4, fp4_supported
+
+        if fp4_supported(w, act):
+            if on_gpu(x):
+                img, simg = fp4.image(w)
+                return native().gemv_fp4(x.contiguous(), img, simg, None, act, False, None, residual, norm_eps)
+            w = dequantize_mxfp4(*fp4.get(w))
     if on_gpu(x):
         x = x.contiguous()
         if fp8 is not None:

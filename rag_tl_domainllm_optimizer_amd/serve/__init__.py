@@ -52,13 +52,14 @@ def serve(cfg, host: str = "127.0.0.1", port: int = 8000, max_batch: int = 16, m
           continuous: bool = True):
     import uvicorn
 
-    from ..cli import build_stack
+    from ..cli import apply_fp4, build_stack
     from ..generation import SamplingParams
     from ..parallel import init
     from ..rag import RagPipeline
 
     di = init()
     st = build_stack(cfg, di.device)
+    apply_fp4(cfg, st["policy"])
     sp = SamplingParams(max_new_tokens=cfg.ppo.max_new_tokens, temperature=cfg.eval.temperature,
                         do_sample=cfg.eval.do_sample, top_k=cfg.eval.top_k)
     rag = RagPipeline(st["encoder"], st["index"], st["docs"], st["policy"], st["tokenizer"], cfg.retrieval.top_k, sp,

@@ -30,6 +30,10 @@ class ContinuousEngine:
     def __init__(self, pipeline, chunk: int = 4):
         if pipeline.sampling.lookup_tokens > 0:
             raise NotImplementedError("prompt-lookup decoding is not supported with continuous batching")
+        layers = getattr(pipeline.gen.model, "layers", None)
+        if layers and getattr(layers[0], "fp4_decode", False) and pipeline.max_batch > 16:
+            raise ValueError(f"continuous batching with MXFP4 decode (model.fp4_decode): max_batch {pipeline.max_batch} "
+                             f"exceeds the 16 rows of the MXFP4 decode kernels")
         self.pipeline = pipeline
         self.chunk = max(1, chunk)
         self._q: "queue.Queue" = queue.Queue()
