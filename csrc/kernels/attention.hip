@@ -2103,8 +2103,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_kernel(AttnBwdArgs a) {
 #pragma unroll
   for (int c = 0; c < DT; ++c) { dk[c] = f32x4{0.f, 0.f, 0.f, 0.f}; dvv[c] = f32x4{0.f, 0.f, 0.f, 0.f}; }
 
-  int qbeg = a.causal ? kb0 : 0;
-  qbeg = max(qbeg, start) & ~63;
+  // causal: a query sees key >= start only from row max(key, start) on. Bidirectional: every query
+  // row sees the keys right of start, the rows left of start included (kv_start masks keys only)
+  const int qbeg = a.causal ? max(kb0, start) & ~63 : 0;
   int qend = a.S;
   if (a.window > 0) qend = min(qend, kb0 + 63 + a.window);
   const bool key_valid = mykey >= start && mykey < a.S;

@@ -98,11 +98,14 @@ def swiglu_bwd(gu, dy):
 
 def attention(q, k, v, B, Sq, Sk, Hq, Hkv, D, causal=True, window=0, scale=None, kv_start=None, kv_len=None,
               rel_bias=None, rb_L=0):
-    """Token-major attention: q [B*Sq, >=Hq*D], k/v [B*Sk, >=Hkv*D] -> (o [B*Sq, Hq*D], lse [B,Hq,Sq])."""
+    """Token-major attention: q [B*Sq, >=Hq*D], k/v [B*Sk, >=Hkv*D] -> (o [B*Sq, Hq*D], lse [B,Hq,Sq]).
+    A query that sees no key has o = 0 and lse = +inf (the kernels' contract). fp64 inputs are
+    evaluated in fp64 (the tests' second oracle), everything else in fp32."""
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
-    qh = q[:, : Hq * D].float().reshape(B, Sq, Hq, D).transpose(1, 2)
-    kh = k[:, : Hkv * D].float().reshape(B, Sk, Hkv, D).transpose(1, 2)
-    vh = v[:, : Hkv * D].float().reshape(B, Sk, Hkv, D).transpose(1, 2)
+    ft = torch.float64 if q.dtype == torch.float64 else torch.float32
+    qh = q[:, : Hq * D].to(ft).reshape(B, Sq, Hq, D).transpose(1, 2)
+    kh = k[:, : Hkv * D].to(ft).reshape(B, Sk, Hkv, D).transpose(1, 2)
+    vh = v[:, : Hkv * D].to(ft).reshape(B, Sk, Hkv, D).transpose(1, 2)
     rep = Hq // Hkv
     kh = kh.repeat_interleave(rep, dim=1)
     vh = vh.repeat_interleave(rep, dim=1)
