@@ -20,6 +20,7 @@
 #include "rt_workspace.h"
 
 #include <cmath>
+#include <type_traits>
 
 namespace rt {
 
@@ -381,10 +382,88 @@ static int gemv_cus() {
   return n;
 }
 
-// Tail of the 16-row no-split kernels (bf16 / fp8 / MXFP4 images): the waves' partial sums meet in
-// LDS and are summed in wave order, then in-GEMM RMS-norm scaling, per-column scale (W8), bias,
-// activation or the SwiGLU gate / up pair, residual, bf16 / fp32 store.
-template <bool OUT_F32, bool PAIR, bool W8, int NW>
+// ---------------------------------------------------------------------------------------------
+// Decode GEMV (M <= 16) without split-K: one workgroup per 16 weight rows of a tile-ordered image
+// ---------------------------------------------------------------------------------------------
+// The split-K decode kernel above ends in a serial hand-off (write-through slab stores drained,
+// an arrival ticket, the last arriver's slab loads): about three dependent device-memory round
+// trips after the last weight byte lands. Here a workgroup owns one 16-row group of the
+// tile-ordered image (its K chunks are ONE contiguous run of nc x 2 KiB) and its NW waves split K;
+// the partial sums meet in LDS, so the tail is a workgroup barrier. N / 16 workgroups (256 for
+// o / down, 384 for qkv) fill the chip without a K split. Each wave keeps DEPTH - 1 k-chunks in
+// flight (non-temporal: every weight byte is read once per step). The M <= 16 rows of X are the
+// MFMA's 16 A rows. Same epilogue contract as gemm_decode_kernel: in-GEMM RMS norm (folded weight,
+// per-row rstd from the X fragments), bias, activation, residual, bf16 / fp32 store; SwiGLU as a
+// gate / up row-group pair. Batch 1: 3.28 -> 2.92 ms/token (profiles/decode_b1_gemv16_ab.log).
+//
+// PAIR (SwiGLU, weight = [gate; up], 2F rows): the workgroup owns output columns [16 grp, 16 grp +
+// 16) and streams the gate row group grp and the up row group F / 16 + grp side by side.
+//
+// One kernel, three weight images: bf16, fp8 (W8A16, config 5) and MXFP4 (W4A16,
+// model.fp4_decode). They differ in one integer S: a lane's 16-B weight load holds 8 S consecutive
+// k of one row (S = 1 bf16, 2 fp8, 4 MXFP4). From S:
+//  * image: per 16-row group G, 2-KiB chunks c of KC = 64 S k, consecutive in c. 16-B unit i is
+//    lane l = i & 63 of load h = (i >> 6) & 1 of tile i >> 7 = (G, c) and holds row 16 G + (l & 15)
+//    at k [c KC + h KC / 2 + (l >> 4) 8 S, + 8 S) (gemv16_image_unit), so every load instruction of
+//    a wave reads one contiguous 1-KiB run;
+//  * X: lane (r, g) loads row r at k [g 8 S + c KC + h KC / 2 + 8 j, + 8) for h = 0, 1 and j < S,
+//    the k of dword group j of its weight load h: both MFMA operands share the k-slot permutation,
+//    so the MFMA sums the right products;
+//  * 2 S MFMAs per accumulator and chunk: MFMA h S + j takes X load (h, j) and Fmt::frag(weight
+//    load h, j, scale of load h). All acc MFMAs in load order, then all accu MFMAs (PAIR), then
+//    the sum of squares over the X loads in load order.
+// Per format, nothing but the widening in frag and:
+//  * fp8: e4m3fn bytes, 4 per dword; per-column scales sb[col] applied in the epilogue.
+//  * MXFP4: OCP MX weights — e2m1 codes, two per byte (element 2 i in the low nibble of byte i),
+//    one E8M0 scale byte per 32 consecutive k of a row, which is exactly one load: one scale byte
+//    per load, applied by the hardware e2m1 -> bf16 conversion (exact: an MXFP4 weight is a bf16
+//    number). Scale image: one 16-bit word per (chunk, lane) = the scale bytes of loads h = 0
+//    (low) and 1 (high), 128 contiguous bytes per wave and chunk, loaded in the same pipeline
+//    stage as the codes. B points to the code image.
+__device__ __forceinline__ bf16x8 fp4x8_to_bf16(unsigned v, float scale) {
+  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+  const bf16x2_t a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 0);
+  const bf16x2_t b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 1);
+  const bf16x2_t c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 2);
+  const bf16x2_t d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 3);
+  return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
+// E8M0 byte s -> 2^(s - 127) as a float (s = 0 is the fp32 denormal 2^-127)
+__device__ __forceinline__ float e8m0_to_float(unsigned s) {
+  return __uint_as_float(s ? (s << 23) : 0x00400000u);
+}
+
+// dword j of a 16-B load (j a compile-time constant after unrolling)
+__device__ __forceinline__ unsigned dword_of(const uint4& v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
+
+// Weight-image traits: S, whether a per-load scale word exists (SCALED: the scale image), whether
+// the epilogue applies per-column scales p.sb (COL_SCALE), and frag = the bf16x8 B fragment of
+// dword group j of one weight load (scale = that load's scale byte when SCALED).
+struct ImgBf16 {
+  static constexpr int S = 1;
+  static constexpr bool SCALED = false, COL_SCALE = false;
+  static __device__ __forceinline__ bf16x8 frag(const uint4& w, int, unsigned) { return __builtin_bit_cast(bf16x8, w); }
+};
+struct ImgFp8 {
+  static constexpr int S = 2;
+  static constexpr bool SCALED = false, COL_SCALE = true;
+  static __device__ __forceinline__ bf16x8 frag(const uint4& w, int j, unsigned) {
+    return fp8x8_to_bf16(dword_of(w, 2 * j), dword_of(w, 2 * j + 1));
+  }
+};
+struct ImgFp4 {
+  static constexpr int S = 4;
+  static constexpr bool SCALED = true, COL_SCALE = false;
+  static __device__ __forceinline__ bf16x8 frag(const uint4& w, int j, unsigned scale) {
+    return fp4x8_to_bf16(dword_of(w, j), e8m0_to_float(scale));
+  }
+};
+
+// Tail of the 16-row kernel: the waves' partial sums meet in LDS and are summed in wave order, then
+// in-GEMM RMS-norm scaling, per-column scale (Fmt::COL_SCALE), bias, activation or the SwiGLU
+// gate / up pair, residual, bf16 / fp32 store.
+template <class Fmt, bool OUT_F32, bool PAIR, int NW>
 __device__ __forceinline__ void gemv16_finish(const GemmArgs& p, const f32x4& acc, const f32x4& accu, float sq,
                                               float (&red)[NW][16][PAIR ? 33 : 17], float (&rsq)[NW][16], int grp) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -420,11 +499,11 @@ __device__ __forceinline__ void gemv16_finish(const GemmArgs& p, const f32x4& ac
     if constexpr (PAIR) {
       const int F = p.N / 2;
       float up = uu * rs;
-      if constexpr (W8) { y *= p.sb[col]; up *= p.sb[F + col]; }
+      if constexpr (Fmt::COL_SCALE) { y *= p.sb[col]; up *= p.sb[F + col]; }
       if (p.bias) { y += bf2f(p.bias[col]); up += bf2f(p.bias[F + col]); }
       y = y / (1.f + __expf(-y)) * up;
     } else {
-      if constexpr (W8) y *= p.sb[col];
+      if constexpr (Fmt::COL_SCALE) y *= p.sb[col];
       if (p.bias) y += bf2f(p.bias[col]);
       y = apply_act(y, p.act);
       if (p.R) y += bf2f(p.R[(long)row * p.ldr + col]);
@@ -434,202 +513,67 @@ __device__ __forceinline__ void gemv16_finish(const GemmArgs& p, const f32x4& ac
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// Decode GEMV (M <= 16) without split-K: one workgroup per 16 weight rows of a tile-ordered image
-// ---------------------------------------------------------------------------------------------
-// The split-K decode kernel above ends in a serial hand-off (write-through slab stores drained,
-// an arrival ticket, the last arriver's slab loads): about three dependent device-memory round
-// trips after the last weight byte lands. Here a workgroup owns one 16-row group of the
-// tile-ordered image (its K chunks are ONE contiguous run of nc x 2 KiB) and its 4 waves split K;
-// the partial sums meet in LDS, so the tail is a workgroup barrier. N / 16 workgroups (256 for
-// o / down, 384 for qkv) fill the chip without a K split. Each wave keeps DEPTH - 1 k-chunks in
-// flight (non-temporal: every weight byte is read once per step). The M <= 16 rows of X are the
-// MFMA's 16 A rows. Same epilogue contract as gemm_decode_kernel: in-GEMM RMS norm (folded weight,
-// per-row rstd from the X fragments), bias, activation, residual, bf16 / fp32 store; SwiGLU as a
-// gate / up row-group pair. Batch 1: 3.28 -> 2.92 ms/token (profiles/decode_b1_gemv16_ab.log).
-//
-// PAIR (SwiGLU, weight = [gate; up], 2F rows): the workgroup owns output columns [16 grp, 16 grp +
-// 16) and streams the gate row group grp and the up row group F / 16 + grp side by side.
-//
-// W8 (W8A16, config 5): the image is the fp8 tile order of shuffle_decode_weight_fp8 — per 16-row
-// group, 2-KiB chunks of 128 k; load h of lane l = 16 g + r holds the 16 e4m3fn bytes of row r at
-// k [128 c + 64 h + 16 g, +16), widened in registers to two bf16x8 fragments (k-slot permutation
-// shared with the X fragments, so the MFMA sums the same products). Half the bytes per chunk of k
-// of the bf16 image; per-column scales sb[col] applied in the epilogue.
-template <bool OUT_F32, int DEPTH, bool PAIR, bool W8 = false, int NW = 4>
-__global__ __launch_bounds__(64 * NW) void gemv16_kernel(GemmArgs p) {
+// simg: the scale image (Fmt::SCALED), else unused
+template <class Fmt, bool OUT_F32, int DEPTH, bool PAIR, int NW>
+__global__ __launch_bounds__(64 * NW) void gemv16_kernel(GemmArgs p, const unsigned short* __restrict__ simg) {
   // M <= 16 rows of X: the MFMA's 16 A rows (row frow of lane (frow, g); rows >= M repeat M - 1)
   // NW waves split the group's K chunks (NW = 8: twice the weight bytes in flight per workgroup)
   __shared__ float red[NW][16][PAIR ? 33 : 17];
   __shared__ float rsq[NW][16];
+  constexpr int S = Fmt::S, KC = 64 * S;  // k per 2-KiB chunk
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int frow = lane & 15, g = lane >> 4;
   const int grp = blockIdx.x;  // 16-row group (of the gate rows when PAIR)
-  constexpr int KC = W8 ? 128 : 64;  // k per 2-KiB chunk
   const int nc = p.K / KC;
-  const int c_begin = wid * nc / NW, c_end = (wid + 1) * nc / NW;
-  const char* wbase = (const char*)p.B + (long)grp * nc * 2048 + lane * 16;
-  const char* ubase = PAIR ? (const char*)p.B + ((long)(p.N / 32) + grp) * nc * 2048 + lane * 16 : wbase;
-  const bf16_t* xrow = p.A + (long)min(frow, p.M - 1) * p.lda + g * (W8 ? 16 : 8);
-  struct Regs { uint4 w0, w1, u0, u1, x0, x1, x2, x3; };
-  auto ld = [&](Regs& r, int c) {
-    r.w0 = load_nt16(wbase + (long)c * 2048);
-    r.w1 = load_nt16(wbase + (long)c * 2048 + 1024);
-    if constexpr (PAIR) {
-      r.u0 = load_nt16(ubase + (long)c * 2048);
-      r.u1 = load_nt16(ubase + (long)c * 2048 + 1024);
-    }
-    if constexpr (W8) {  // k [128 c + 64 h + 16 g, +16) as two 8-element halves, h = 0, 1
-      r.x0 = *(const uint4*)(xrow + c * 128);
-      r.x1 = *(const uint4*)(xrow + c * 128 + 8);
-      r.x2 = *(const uint4*)(xrow + c * 128 + 64);
-      r.x3 = *(const uint4*)(xrow + c * 128 + 72);
-    } else {
-      r.x0 = *(const uint4*)(xrow + c * 64);
-      r.x1 = *(const uint4*)(xrow + c * 64 + 32);
-    }
-  };
-  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f}, accu = acc;
-  float sq = 0.f;
-  const bool normed = p.norm_eps > 0.f;
-  auto mma = [&](const Regs& r) {
-    if constexpr (W8) {
-      const bf16x8 x0 = __builtin_bit_cast(bf16x8, r.x0), x1 = __builtin_bit_cast(bf16x8, r.x1);
-      const bf16x8 x2 = __builtin_bit_cast(bf16x8, r.x2), x3 = __builtin_bit_cast(bf16x8, r.x3);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x0, fp8x8_to_bf16(r.w0.x, r.w0.y), acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1, fp8x8_to_bf16(r.w0.z, r.w0.w), acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x2, fp8x8_to_bf16(r.w1.x, r.w1.y), acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x3, fp8x8_to_bf16(r.w1.z, r.w1.w), acc, 0, 0, 0);
-      if constexpr (PAIR) {
-        accu = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x0, fp8x8_to_bf16(r.u0.x, r.u0.y), accu, 0, 0, 0);
-        accu = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1, fp8x8_to_bf16(r.u0.z, r.u0.w), accu, 0, 0, 0);
-        accu = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x2, fp8x8_to_bf16(r.u1.x, r.u1.y), accu, 0, 0, 0);
-        accu = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x3, fp8x8_to_bf16(r.u1.z, r.u1.w), accu, 0, 0, 0);
-      }
-    } else {
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, r.x0), __builtin_bit_cast(bf16x8, r.w0), acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, r.x1), __builtin_bit_cast(bf16x8, r.w1), acc, 0, 0, 0);
-      if constexpr (PAIR) {
-        accu = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, r.x0), __builtin_bit_cast(bf16x8, r.u0), accu, 0, 0, 0);
-        accu = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, r.x1), __builtin_bit_cast(bf16x8, r.u1), accu, 0, 0, 0);
-      }
-    }
-    if (normed) {
-      float f[8];
-      unpack8(r.x0, f);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) sq += f[e] * f[e];
-      unpack8(r.x1, f);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) sq += f[e] * f[e];
-      if constexpr (W8) {
-        unpack8(r.x2, f);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sq += f[e] * f[e];
-        unpack8(r.x3, f);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sq += f[e] * f[e];
-      }
-    }
-  };
-  Regs r[DEPTH];
-#pragma unroll
-  for (int i = 0; i < DEPTH - 1; ++i)
-    if (c_begin + i < c_end) ld(r[i], c_begin + i);
-  int c = c_begin;
-  for (; c + DEPTH <= c_end; c += DEPTH) {
-#pragma unroll
-    for (int i = 0; i < DEPTH; ++i) {
-      if (c + i + DEPTH - 1 < c_end) ld(r[(i + DEPTH - 1) % DEPTH], c + i + DEPTH - 1);
-      mma(r[i]);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < DEPTH - 1; ++i)
-    if (c + i < c_end) mma(r[i]);
-  gemv16_finish<OUT_F32, PAIR, W8, NW>(p, acc, accu, sq, red, rsq, grp);
-}
-
-// MXFP4 (W4A16, model.fp4_decode) form of the 16-row kernel: OCP MX weights — e2m1 codes, two per
-// byte, one E8M0 scale byte per 32 consecutive k of a row — a quarter of the bf16 weight bytes.
-// Image (shuffle_decode_weight_fp4): per 16-row group G, 2-KiB chunks of 256 k; load h = 0, 1 of
-// lane l = 16 g + r holds the 16 code bytes of row 16 G + r at k [256 c + 128 h + 32 g, +32): one
-// whole MX block, so one scale byte per load. Dword j of the load is k [.. + 8 j, +8) in order
-// (element 2 i in the low nibble of byte i), widened by the hardware e2m1 -> bf16 conversion with
-// the block's scale applied (exact: an MXFP4 weight is a bf16 number) into the B fragment of MFMA
-// j; the X fragment of MFMA j is the lane's 16 B at the same k, so both operands agree on the
-// k-slot permutation and the MFMA sums the right products. Scale image: one 16-bit word per (chunk,
-// lane) = the scale bytes of loads h = 0 (low) and 1 (high), 128 contiguous bytes per wave and
-// chunk, loaded in the same pipeline stage as the codes. B points to the code image; the epilogue
-// (gemv16_finish) and the wave-order sum of the partials are those of the bf16 kernel.
-__device__ __forceinline__ bf16x8 fp4x8_to_bf16(unsigned v, float scale) {
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-  const bf16x2_t a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 0);
-  const bf16x2_t b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 1);
-  const bf16x2_t c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 2);
-  const bf16x2_t d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, scale, 3);
-  return bf16x8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
-}
-
-// E8M0 byte s -> 2^(s - 127) as a float (s = 0 is the fp32 denormal 2^-127)
-__device__ __forceinline__ float e8m0_to_float(unsigned s) {
-  return __uint_as_float(s ? (s << 23) : 0x00400000u);
-}
-
-template <bool OUT_F32, int DEPTH, bool PAIR, int NW>
-__global__ __launch_bounds__(64 * NW) void gemv16_fp4_kernel(GemmArgs p, const unsigned short* __restrict__ simg) {
-  __shared__ float red[NW][16][PAIR ? 33 : 17];
-  __shared__ float rsq[NW][16];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int frow = lane & 15, g = lane >> 4;
-  const int grp = blockIdx.x;  // 16-row group (of the gate rows when PAIR)
-  const int nc = p.K / 256;
   const int c_begin = wid * nc / NW, c_end = (wid + 1) * nc / NW;
   const long ugrp = PAIR ? (long)(p.N / 32) + grp : grp;
   const char* wbase = (const char*)p.B + (long)grp * nc * 2048 + lane * 16;
   const char* ubase = (const char*)p.B + ugrp * nc * 2048 + lane * 16;
   const unsigned short* sbase = simg + (long)grp * nc * 64 + lane;
   const unsigned short* subase = simg + ugrp * nc * 64 + lane;
-  const bf16_t* xrow = p.A + (long)min(frow, p.M - 1) * p.lda + g * 32;
-  struct Regs { uint4 w0, w1, u0, u1, x[8]; unsigned sw, su; };
+  const bf16_t* xrow = p.A + (long)min(frow, p.M - 1) * p.lda + g * (8 * S);
+  struct Regs { uint4 w[2], u[2], x[2 * S]; unsigned sw, su; };  // u, su: PAIR; sw, su: Fmt::SCALED
   auto ld = [&](Regs& r, int c) {
-    r.w0 = load_nt16(wbase + (long)c * 2048);
-    r.w1 = load_nt16(wbase + (long)c * 2048 + 1024);
-    r.sw = __builtin_nontemporal_load(sbase + (long)c * 64);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) r.w[h] = load_nt16(wbase + (long)c * 2048 + h * 1024);
+    if constexpr (Fmt::SCALED) r.sw = __builtin_nontemporal_load(sbase + (long)c * 64);
     if constexpr (PAIR) {
-      r.u0 = load_nt16(ubase + (long)c * 2048);
-      r.u1 = load_nt16(ubase + (long)c * 2048 + 1024);
-      r.su = __builtin_nontemporal_load(subase + (long)c * 64);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) r.u[h] = load_nt16(ubase + (long)c * 2048 + h * 1024);
+      if constexpr (Fmt::SCALED) r.su = __builtin_nontemporal_load(subase + (long)c * 64);
     }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {  // k [256 c + 128 h + 32 g + 8 j, +8), h = 0, 1
-      r.x[j] = *(const uint4*)(xrow + c * 256 + 8 * j);
-      r.x[4 + j] = *(const uint4*)(xrow + c * 256 + 128 + 8 * j);
-    }
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int j = 0; j < S; ++j) r.x[h * S + j] = *(const uint4*)(xrow + c * KC + h * (KC / 2) + 8 * j);
   };
   f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f}, accu = acc;
   float sq = 0.f;
   const bool normed = p.norm_eps > 0.f;
+  auto scale = [](const unsigned& s, int h) -> unsigned {  // scale byte of load h (s: a 16-bit word)
+    if constexpr (Fmt::SCALED) return h ? s >> 8 : s & 0xffu;
+    else return 0u;
+  };
   auto mma = [&](const Regs& r) {
-    const unsigned w[8] = {r.w0.x, r.w0.y, r.w0.z, r.w0.w, r.w1.x, r.w1.y, r.w1.z, r.w1.w};
-    const float sw[2] = {e8m0_to_float(r.sw & 0xffu), e8m0_to_float(r.sw >> 8)};
 #pragma unroll
-    for (int j = 0; j < 8; ++j)
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, r.x[j]), fp4x8_to_bf16(w[j], sw[j >> 2]), acc,
-                                                    0, 0, 0);
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int j = 0; j < S; ++j)
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, r.x[h * S + j]),
+                                                      Fmt::frag(r.w[h], j, scale(r.sw, h)), acc, 0, 0, 0);
     if constexpr (PAIR) {
-      const unsigned u[8] = {r.u0.x, r.u0.y, r.u0.z, r.u0.w, r.u1.x, r.u1.y, r.u1.z, r.u1.w};
-      const float su[2] = {e8m0_to_float(r.su & 0xffu), e8m0_to_float(r.su >> 8)};
 #pragma unroll
-      for (int j = 0; j < 8; ++j)
-        accu = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, r.x[j]), fp4x8_to_bf16(u[j], su[j >> 2]),
-                                                       accu, 0, 0, 0);
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int j = 0; j < S; ++j)
+          accu = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, r.x[h * S + j]),
+                                                         Fmt::frag(r.u[h], j, scale(r.su, h)), accu, 0, 0, 0);
     }
     if (normed) {
       float f[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        unpack8(r.x[j], f);
+      for (int i = 0; i < 2 * S; ++i) {
+        unpack8(r.x[i], f);
 #pragma unroll
         for (int e = 0; e < 8; ++e) sq += f[e] * f[e];
       }
@@ -650,7 +594,7 @@ __global__ __launch_bounds__(64 * NW) void gemv16_fp4_kernel(GemmArgs p, const u
 #pragma unroll
   for (int i = 0; i < DEPTH - 1; ++i)
     if (c + i < c_end) mma(r[i]);
-  gemv16_finish<OUT_F32, PAIR, false, NW>(p, acc, accu, sq, red, rsq, grp);
+  gemv16_finish<Fmt, OUT_F32, PAIR, NW>(p, acc, accu, sq, red, rsq, grp);
 }
 
 // Shared tail of the M <= 64 kernels: split-K hand-off (write-through slabs + ticket, last arriver
@@ -1264,21 +1208,64 @@ static int decode_depth(int MT, long blocks) {
 }
 
 
-extern "C" int rt_gemm_nt(const void* A, long lda, const void* B, long ldb, const void* U, long ldu,
-                          const void* UB, long ldub, int Rp, const void* bias, void* C, long ldc, int M,
-                          int N, int K, int act, int out_f32, float* slabs, unsigned* tickets,
-                          const void* R, long ldr, float norm_eps, int wshuf, hipStream_t stream) {
+// waves per row group of the 16-row kernel: 8 when the grid has at most one workgroup per CU (o /
+// down: N / 16 = 256), so each CU keeps twice the weight bytes in flight; 4 on wider grids (qkv
+// 384, lm_head 2000 workgroups), where 8 measured the same or slower. Batch-1 p50 0.383 -> 0.376 s
+// (profiles/r4/gemv16_waves_ab.log)
+static int gemv16_auto_waves(int grid) { return grid <= gemv_cus() ? 8 : 4; }
+
+// The built forms of gemv16_kernel, per image: bf16 depth 4 at 4 / 8 / 16 waves, depth 6 and 8 at
+// 4 waves, the SwiGLU pair at depth 4 with 4 waves; fp8 depth 4 with 4 waves, bf16 output; MXFP4
+// depth 3 at 4 / 8 waves, the pair at 4. A depth / wave count outside that set takes the default
+// form of the image (pair over depth over waves, as the tuning knobs always resolved).
+template <class Fmt>
+static void launch_gemv16(const GemmArgs& p, const unsigned short* simg, bool out_f32, bool pair, int depth, int nw,
+                          hipStream_t stream) {
+  const dim3 grid(pair ? p.N / 32 : p.N / 16);
+#define GEMV16(F32, D, P, W) hipLaunchKernelGGL((gemv16_kernel<Fmt, F32, D, P, W>), grid, dim3(64 * W), 0, stream, p, simg)
+#define GEMV16_OUT(D, P, W) do { if (out_f32) GEMV16(true, D, P, W); else GEMV16(false, D, P, W); } while (0)
+  if constexpr (std::is_same_v<Fmt, ImgBf16>) {
+    if (pair) GEMV16_OUT(4, true, 4);
+    else if (depth == 6) GEMV16_OUT(6, false, 4);
+    else if (depth == 8) GEMV16_OUT(8, false, 4);
+    else if (nw == 8) GEMV16_OUT(4, false, 8);
+    else if (nw == 16) GEMV16_OUT(4, false, 16);
+    else GEMV16_OUT(4, false, 4);
+  } else if constexpr (std::is_same_v<Fmt, ImgFp8>) {
+    if (pair) GEMV16(false, 4, true, 4);
+    else GEMV16(false, 4, false, 4);
+  } else {
+    if (pair) GEMV16_OUT(3, true, 4);
+    else if (nw == 8) GEMV16_OUT(3, false, 8);
+    else GEMV16_OUT(3, false, 4);
+  }
+#undef GEMV16_OUT
+#undef GEMV16
+}
+
+// the GemmArgs fields every skinny entry point sets; LoRA operands and fp8 scales start out null
+static GemmArgs skinny_args(const void* A, long lda, const void* B, long ldb, const void* bias, void* C, long ldc, int M,
+                            int N, int K, int act, const void* R, long ldr, float norm_eps, int wshuf) {
   GemmArgs p;
   p.A = (const bf16_t*)A; p.lda = lda;
   p.B = (const bf16_t*)B; p.ldb = ldb;
-  p.U = (const bf16_t*)U; p.ldu = ldu;
-  p.UB = (const bf16_t*)UB; p.ldub = ldub;
-  p.Rp = (U && UB) ? Rp : 0;
+  p.U = nullptr; p.ldu = 0; p.UB = nullptr; p.ldub = 0; p.Rp = 0;
   p.bias = (const bf16_t*)bias;
   p.C = C; p.ldc = ldc;
   p.M = M; p.N = N; p.K = K; p.act = act;
   p.sa = nullptr; p.sb = nullptr;
   p.R = (const bf16_t*)R; p.ldr = ldr; p.norm_eps = norm_eps; p.wshuf = wshuf;
+  return p;
+}
+
+extern "C" int rt_gemm_nt(const void* A, long lda, const void* B, long ldb, const void* U, long ldu,
+                          const void* UB, long ldub, int Rp, const void* bias, void* C, long ldc, int M,
+                          int N, int K, int act, int out_f32, float* slabs, unsigned* tickets,
+                          const void* R, long ldr, float norm_eps, int wshuf, hipStream_t stream) {
+  GemmArgs p = skinny_args(A, lda, B, ldb, bias, C, ldc, M, N, K, act, R, ldr, norm_eps, wshuf);
+  p.U = (const bf16_t*)U; p.ldu = ldu;
+  p.UB = (const bf16_t*)UB; p.ldub = ldub;
+  p.Rp = (U && UB) ? Rp : 0;
   if (M <= 0 || N <= 0) return 0;
   if (wshuf && (M > 64 || N % 16 != 0 || K % 64 != 0)) return -4;  // shuffled weights: decode kernel only
   if (act == ACT_SWIGLU && (M > 64 || N % 64 != 0 || (U && UB))) return -2;
@@ -1307,26 +1294,11 @@ extern "C" int rt_gemm_nt(const void* A, long lda, const void* B, long ldb, cons
     if (out_f32) hipLaunchKernelGGL((gemm_m64_kernel<true>), grid, block, 0, stream, p, slabs, tickets, split);
     else hipLaunchKernelGGL((gemm_m64_kernel<false>), grid, block, 0, stream, p, slabs, tickets, split);
   } else if (M <= gemv16_max_m() && wshuf && tuning().decode_split == 0 && use_gemv16(N, K, act) && p.Rp == 0) {
+    // waves per row group: tuning gemv16_waves, 0 = auto
     const bool pair = act == ACT_SWIGLU;
-    dim3 grid(pair ? N / 32 : N / 16), block(256);
-    const int gd = tuning().gemv16_depth;
-#define G16(D, P) if (out_f32) hipLaunchKernelGGL((gemv16_kernel<true, D, P>), grid, block, 0, stream, p); \
-                  else hipLaunchKernelGGL((gemv16_kernel<false, D, P>), grid, block, 0, stream, p);
-    // waves per row group: 0 = auto — 8 when the grid has at most one workgroup per CU (o / down:
-    // N / 16 = 256), so each CU keeps twice the weight bytes in flight; 4 on wider grids (qkv 384,
-    // lm_head 2000 workgroups), where 8 measured the same or slower. Batch-1 p50 0.383 -> 0.376 s
-    // (profiles/r4/gemv16_waves_ab.log)
     int nw = tuning().gemv16_waves;
-    if (nw == 0) nw = (int)grid.x <= gemv_cus() ? 8 : 4;
-    if (pair) { G16(4, true) } else if (gd == 6) { G16(6, false) } else if (gd == 8) { G16(8, false) }
-    else if (nw == 8) {
-      if (out_f32) hipLaunchKernelGGL((gemv16_kernel<true, 4, false, false, 8>), grid, dim3(512), 0, stream, p);
-      else hipLaunchKernelGGL((gemv16_kernel<false, 4, false, false, 8>), grid, dim3(512), 0, stream, p);
-    } else if (nw == 16) {
-      if (out_f32) hipLaunchKernelGGL((gemv16_kernel<true, 4, false, false, 16>), grid, dim3(1024), 0, stream, p);
-      else hipLaunchKernelGGL((gemv16_kernel<false, 4, false, false, 16>), grid, dim3(1024), 0, stream, p);
-    } else { G16(4, false) }
-#undef G16
+    if (nw == 0) nw = gemv16_auto_waves(pair ? N / 32 : N / 16);
+    launch_gemv16<ImgBf16>(p, nullptr, out_f32, pair, tuning().gemv16_depth, nw, stream);
   } else {
     const int MT = (M + 15) / 16;
     const int want = wshuf ? decode_split_shuf(K) : decode_split(N, K);
@@ -1356,7 +1328,7 @@ extern "C" int rt_gemm_big_fp8(const void*, long, const float*, const void*, lon
 // fp8 GEMMs: C[M,N] (bf16) = act( (A_q B_q^T) * sa[row] * sb[col] + bias ), A_q / B_q OCP e4m3fn.
 //  * M > 64 : W8A8 on the gemm_big schedule, MX-scaled mfma_16x16x128_f8f6f4 (2x the bf16 rate)
 //  * M <= 64: W8A16 (A = bf16 activations, sa ignored): half the weight bytes.
-//      - M <= 16 with the tile-ordered fp8 image (wshuf, shuffle_decode_weight_fp8): gemv16_kernel<W8>,
+//      - M <= 16 with the tile-ordered fp8 image (wshuf, shuffle_decode_weight_fp8): gemv16_kernel<ImgFp8>,
 //        one workgroup per 16 weight rows, no split-K;
 //      - 16 < M <= 64 with the image: the LDS-DMA ring gemm_m64_kernel<W8> (split-K slabs);
 //      - row-major fp8 weights (no image: small / odd shapes): the split-K register-streaming kernel.
@@ -1364,12 +1336,8 @@ extern "C" int rt_gemm_fp8(const void* A, long lda, const float* sa, const void*
                            const void* bias, void* C, long ldc, int M, int N, int K, int act, int a_is_bf16,
                            float* slabs, unsigned* tickets, const void* R, long ldr, float norm_eps, int wshuf,
                            hipStream_t stream) {
-  GemmArgs p;
-  p.A = (const bf16_t*)A; p.lda = lda; p.B = (const bf16_t*)B; p.ldb = ldb;
-  p.U = nullptr; p.ldu = 0; p.UB = nullptr; p.ldub = 0; p.Rp = 0;
-  p.bias = (const bf16_t*)bias; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.act = act;
+  GemmArgs p = skinny_args(A, lda, B, ldb, bias, C, ldc, M, N, K, act, R, ldr, norm_eps, 0);
   p.sa = sa; p.sb = sb;
-  p.R = (const bf16_t*)R; p.ldr = ldr; p.norm_eps = norm_eps; p.wshuf = 0;
   if (M <= 0 || N <= 0) return 0;
   if ((R || norm_eps > 0.f) && !a_is_bf16) return -3;
   if (a_is_bf16) {
@@ -1380,9 +1348,7 @@ extern "C" int rt_gemm_fp8(const void* A, long lda, const float* sa, const void*
       // LDS-DMA ring above
       if (K % 128 || N % 16 || (pair && N % 64)) return -4;
       if (M <= 16 && tuning().gemm_variant != 4) {
-        dim3 grid(pair ? N / 32 : N / 16), block(256);
-        if (pair) hipLaunchKernelGGL((gemv16_kernel<false, 4, true, true>), grid, block, 0, stream, p);
-        else hipLaunchKernelGGL((gemv16_kernel<false, 4, false, true>), grid, block, 0, stream, p);
+        launch_gemv16<ImgFp8>(p, nullptr, false, pair, 4, 4, stream);
       } else if (N % 256 == 0 && tuning().gemm_variant != 5) {
         // 256 weight rows per workgroup (X read N / 256 times); RT variant 5 = the 64-column ring
         int split = slabs ? fit_split(wide_split(N, K), N / 256, WD_SLAB) : 1;
@@ -1426,61 +1392,69 @@ extern "C" int rt_gemm_fp8(const void* A, long lda, const float* sa, const void*
   return 0;
 }
 
-// Decode-weight image for the M <= 64 kernel: W [N, K] row-major -> per (16-row group G, 64-k chunk
-// c) one 2-KiB tile in the order the kernel's lanes load it (lane l = 16 g + r of load h reads
-// W[16 G + r][64 c + 32 h + 8 g .. +8]), tiles of one row group consecutive in c. Every 16-B load
-// instruction of a wave then reads one contiguous 1-KiB run (tools/microbench/hbm_pattern.hip:
-// 6.3-6.7 TB/s vs 5.9 for the row-major 16-rows x 128-B pattern). Measured at M = 1 (graph replay,
-// cold weights, profiles/kernels_decode_depth_shuffle.log): the split-K launches gain (qkv 14.2 ->
-// 12.8 us, o 11.0 -> 10.3, down 28.5 -> 21.9), the unsplit wide ones do not (gate_up 52.7 -> 51.3,
-// lm_head 49.7 -> 56.9; rotating each block's k walk made both worse) until they are split 8 ways
-// too (decode_split_shuf: gate_up 43.2, lm_head 47.7). At the same split the results are bitwise
-// identical to the row-major launch. One thread per 16 B.
+// Decode-weight images (layout rule: the 16-row kernel's comment). Row-major W [N, K] -> per (16-row
+// group G, 64 S-k chunk c) one 2-KiB tile in the order the kernel's lanes load it, tiles of one row
+// group consecutive in c; S = 1 bf16 (also read by gemm_decode_kernel with wshuf), 2 fp8 bytes, 4
+// MXFP4 codes. Every 16-B load instruction of a wave then reads one contiguous 1-KiB run
+// (tools/microbench/hbm_pattern.hip: 6.3-6.7 TB/s vs 5.9 for the row-major 16-rows x 128-B
+// pattern). Measured at M = 1 (graph replay, cold weights,
+// profiles/kernels_decode_depth_shuffle.log): the split-K launches gain (qkv 14.2 -> 12.8 us, o
+// 11.0 -> 10.3, down 28.5 -> 21.9), the unsplit wide ones do not (gate_up 52.7 -> 51.3, lm_head
+// 49.7 -> 56.9; rotating each block's k walk made both worse) until they are split 8 ways too
+// (decode_split_shuf: gate_up 43.2, lm_head 47.7). At the same split the results are bitwise
+// identical to the row-major launch.
+//
+// 16-B unit i of an image -> the row and first k (of 8 S) it holds; nc = chunks per row group
+template <int S>
+__device__ __forceinline__ void gemv16_image_unit(long i, long nc, long& row, long& k) {
+  const long l = i & 63, h = (i >> 6) & 1, tile = i >> 7;
+  const long G = tile / nc, c = tile % nc;
+  row = G * 16 + (l & 15);
+  k = c * (64 * S) + h * (32 * S) + (l >> 4) * (8 * S);
+}
+
+// One thread per 16 B of weights. S = 4 (scales, simg non-null), second pass: scale word i = lane
+// l = i & 63 of tile i >> 6 holds the scale bytes of the MX blocks of that lane's loads h = 0 (low
+// byte) and h = 1 (high byte, 4 blocks on); one thread per word.
+template <int S>
 __global__ __launch_bounds__(256) void shuffle_decode_weight_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst,
-                                                                     long N, long K) {
-  const long nc = K / 64;
-  const long total = N * K / 8;
+                                                                     const uint8_t* __restrict__ scales,
+                                                                     unsigned short* __restrict__ simg, long N, long K) {
+  const long nc = K / (64 * S);
+  const long total = N * K / (8 * S);
+  long row, k;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const long l = i & 63, h = (i >> 6) & 1, tile = i >> 7;
-    const long G = tile / nc, c = tile % nc;
-    const long row = G * 16 + (l & 15), k = c * 64 + h * 32 + (l >> 4) * 8;
-    dst[i] = src[(row * K + k) / 8];
+    gemv16_image_unit<S>(i, nc, row, k);
+    dst[i] = src[(row * K + k) / (8 * S)];
   }
+  if constexpr (S == 4) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total / 2; i += (long)gridDim.x * 256) {
+      gemv16_image_unit<S>(((i >> 6) << 7) | (i & 63), nc, row, k);
+      const uint8_t* s = scales + (row * K + k) / 32;
+      simg[i] = (unsigned short)((unsigned)s[0] | ((unsigned)s[4] << 8));
+    }
+  }
+}
+
+template <int S>
+static int shuffle_decode_weight(const void* src, void* dst, const void* scales, void* simg, long N, long K,
+                                 hipStream_t stream) {
+  const long total = N * K / (8 * S);
+  const int blocks = (int)std::min<long>((total + 255) / 256, 8192);
+  hipLaunchKernelGGL(shuffle_decode_weight_kernel<S>, dim3(blocks), dim3(256), 0, stream, (const uint4*)src, (uint4*)dst,
+                     (const uint8_t*)scales, (unsigned short*)simg, N, K);
+  RT_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int rt_shuffle_decode_weight(const void* src, void* dst, long N, long K, hipStream_t stream) {
   if (N % 16 || K % 64) return -1;
-  const long total = N * K / 8;
-  const int blocks = (int)std::min<long>((total + 255) / 256, 8192);
-  hipLaunchKernelGGL(shuffle_decode_weight_kernel, dim3(blocks), dim3(256), 0, stream, (const uint4*)src, (uint4*)dst, N, K);
-  RT_LAUNCH_CHECK();
-  return 0;
-}
-
-// fp8 decode-weight image for gemv16_kernel<W8>: q [N, K] e4m3fn bytes row-major -> per (16-row
-// group G, 128-k chunk c) one 2-KiB tile; 16-B unit i of a tile: lane l = i & 63 of load h =
-// (i >> 6) & 1 holds row 16 G + (l & 15), k [128 c + 64 h + 16 (l >> 4), +16). Every load
-// instruction of a wave then reads one contiguous 1-KiB run. One thread per 16 B.
-__global__ __launch_bounds__(256) void shuffle_decode_weight_fp8_kernel(const uint4* __restrict__ src,
-                                                                        uint4* __restrict__ dst, long N, long K) {
-  const long nc = K / 128;
-  const long total = N * K / 16;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const long l = i & 63, h = (i >> 6) & 1, tile = i >> 7;
-    const long G = tile / nc, c = tile % nc;
-    const long row = G * 16 + (l & 15), k = c * 128 + h * 64 + (l >> 4) * 16;
-    dst[i] = src[(row * K + k) / 16];
-  }
+  return shuffle_decode_weight<1>(src, dst, nullptr, nullptr, N, K, stream);
 }
 
 extern "C" int rt_shuffle_decode_weight_fp8(const void* src, void* dst, long N, long K, hipStream_t stream) {
   if (N % 16 || K % 128) return -1;
-  const long total = N * K / 16;
-  const int blocks = (int)std::min<long>((total + 255) / 256, 8192);
-  hipLaunchKernelGGL(shuffle_decode_weight_fp8_kernel, dim3(blocks), dim3(256), 0, stream, (const uint4*)src,
-                     (uint4*)dst, N, K);
-  RT_LAUNCH_CHECK();
-  return 0;
+  return shuffle_decode_weight<2>(src, dst, nullptr, nullptr, N, K, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1531,64 +1505,25 @@ extern "C" int rt_quant_mxfp4(const void* w, void* codes, void* scales, long N, 
   return 0;
 }
 
-// Row-major MXFP4 codes [N, K / 2] + scales [N, K / 32] -> the image of gemv16_fp4_kernel (layout
-// there). Code image: 16-B unit i = lane l = i & 63 of load h = (i >> 6) & 1 of tile i >> 7 =
-// (G, c): row 16 G + (l & 15), MX block 8 c + 4 h + (l >> 4). Scale image: 16-bit word i = lane
-// l = i & 63 of tile i >> 6: the scale bytes of that row's blocks 8 c + (l >> 4) (low byte) and
-// + 4 (high byte). One thread per 16 B of codes, then one per scale word.
-__global__ __launch_bounds__(256) void shuffle_decode_weight_fp4_kernel(const uint4* __restrict__ codes,
-                                                                        const uint8_t* __restrict__ scales,
-                                                                        uint4* __restrict__ img,
-                                                                        unsigned short* __restrict__ simg, long N, long K) {
-  const long nc = K / 256, nb = K / 32;
-  const long total = N * nb;  // 16-B units of codes = MX blocks
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const long l = i & 63, h = (i >> 6) & 1, tile = i >> 7;
-    const long G = tile / nc, c = tile % nc;
-    img[i] = codes[(G * 16 + (l & 15)) * nb + c * 8 + h * 4 + (l >> 4)];
-  }
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total / 2; i += (long)gridDim.x * 256) {
-    const long l = i & 63, tile = i >> 6;
-    const long G = tile / nc, c = tile % nc;
-    const uint8_t* s = scales + (G * 16 + (l & 15)) * nb + c * 8 + (l >> 4);
-    simg[i] = (unsigned short)((unsigned)s[0] | ((unsigned)s[4] << 8));
-  }
-}
-
+// Row-major MXFP4 codes [N, K / 2] + scales [N, K / 32] -> the code and scale images
 extern "C" int rt_shuffle_decode_weight_fp4(const void* codes, const void* scales, void* img, void* simg, long N, long K,
                                             hipStream_t stream) {
   if (N <= 0 || K <= 0 || N % 16 || K % 256) return -1;
-  const long total = N * K / 32;
-  const int blocks = (int)std::min<long>((total + 255) / 256, 8192);
-  hipLaunchKernelGGL(shuffle_decode_weight_fp4_kernel, dim3(blocks), dim3(256), 0, stream, (const uint4*)codes,
-                     (const uint8_t*)scales, (uint4*)img, (unsigned short*)simg, N, K);
-  RT_LAUNCH_CHECK();
-  return 0;
+  return shuffle_decode_weight<4>(codes, img, scales, simg, N, K, stream);
 }
 
 // C[M, N] = epilogue(X[M, K] · W^T), M <= 16, W the MXFP4 image above (N = weight rows, 2 F for
 // SwiGLU). The variant depends on the shape alone, never on M, so a row's arithmetic is the same in
-// a 1-row decode step and a 16-row verify step: 8 waves per row group when the grid has at most one
-// workgroup per CU (the rule of the bf16 kernel), else 4; the SwiGLU pair form runs 4.
+// a 1-row decode step and a 16-row verify step: gemv16_auto_waves, as on the bf16 image; the SwiGLU
+// pair form runs 4 waves.
 extern "C" int rt_gemv_fp4(const void* A, long lda, const void* img, const void* simg, const void* bias, void* C, long ldc,
                            int M, int N, int K, int act, int out_f32, const void* R, long ldr, float norm_eps,
                            hipStream_t stream) {
-  GemmArgs p;
-  p.A = (const bf16_t*)A; p.lda = lda; p.B = (const bf16_t*)img; p.ldb = 0;
-  p.U = nullptr; p.ldu = 0; p.UB = nullptr; p.ldub = 0; p.Rp = 0;
-  p.bias = (const bf16_t*)bias; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.act = act;
-  p.sa = nullptr; p.sb = nullptr;
-  p.R = (const bf16_t*)R; p.ldr = ldr; p.norm_eps = norm_eps; p.wshuf = 1;
+  const GemmArgs p = skinny_args(A, lda, img, 0, bias, C, ldc, M, N, K, act, R, ldr, norm_eps, 1);
   if (M <= 0 || N <= 0) return 0;
   const bool pair = act == ACT_SWIGLU;
   if (M > 16 || K <= 0 || K % 256 || N % 16 || (pair && N % 64) || lda % 8) return -4;
-  dim3 grid(pair ? N / 32 : N / 16);
-  const unsigned short* s = (const unsigned short*)simg;
-#define G4(P, W)                                                                                              \
-  if (out_f32) hipLaunchKernelGGL((gemv16_fp4_kernel<true, 3, P, W>), grid, dim3(64 * W), 0, stream, p, s); \
-  else hipLaunchKernelGGL((gemv16_fp4_kernel<false, 3, P, W>), grid, dim3(64 * W), 0, stream, p, s);
-  if (pair) { G4(true, 4) } else if ((int)grid.x <= gemv_cus()) { G4(false, 8) } else { G4(false, 4) }
-#undef G4
+  launch_gemv16<ImgFp4>(p, (const unsigned short*)simg, out_f32, pair, 3, gemv16_auto_waves(N / 16), stream);
   RT_LAUNCH_CHECK();
   return 0;
 }

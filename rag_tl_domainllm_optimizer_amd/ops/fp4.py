@@ -11,7 +11,7 @@ Format of a bf16 weight ``W [N, K]``, ``K % 32 == 0`` (row-major, public):
 * ``codes [N, K / 2]`` uint8, element ``2 i`` in the low nibble of byte ``i``;
   ``scales [N, K / 32]`` uint8.
 
-A widened MXFP4 weight is exactly a bf16 number, so the decode kernel (``gemv16_fp4_kernel``,
+A widened MXFP4 weight is exactly a bf16 number, so the decode kernel (``gemv16_kernel<ImgFp4>``,
 M <= 16) widens in registers with the hardware e2m1 -> bf16 conversion and runs the bf16 MFMA: a
 quarter of the bf16 weight bytes per token. Round-to-nearest MXFP4 carries ~11 % relative rms
 weight error on Gaussian weights: an opt-in latency / quality trade (docs/DESIGN.md).

@@ -121,6 +121,20 @@ def gemv_case():
 def test_gemv_against_dequantised_product(gemv_case, N, K, M, mode):
     if mode == "swiglu" and N % 64:
         N = 64  # the pair form needs N % 64 == 0: (64, 256) is the one-chunk case of this mode
+    _check_gemv(gemv_case, N, K, M, mode)
+
+
+@pytest.mark.parametrize("K", [256, 1280, 3072, 3328])
+def test_gemv_ring_edges(gemv_case, K):
+    """depth 3, 256 k per chunk, N = 64 (4 row groups: 8 waves, the pair form 4): 1 chunk (the other
+    waves idle), 5 (0-1 per wave at 8 waves, 1-2 at 4: the ring never fills), 12 (exactly DEPTH per
+    wave at 4 waves, 1-2 at 8), 13 (DEPTH + 1 for one of 4 waves, an uneven 1-2 at 8)"""
+    for M in (1, 16):
+        for mode in ("plain", "plain_f32", "norm_residual", "swiglu"):
+            _check_gemv(gemv_case, 64, K, M, mode)
+
+
+def _check_gemv(gemv_case, N, K, M, mode):
     w, d, d_dev, x16, r16, f4, sh = gemv_case(N, K)
     x, r = x16[:M], r16[:M]
     xd, rd = x.to(DEV), r.to(DEV)

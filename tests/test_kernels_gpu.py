@@ -1078,6 +1078,133 @@ def test_gemm_fp8_decode_w8a16(M, N, K, mode):
         _close(out2, y3)
 
 
+# ------------------------------------------- 16-row GEMV: ring edges, rows vs M, image layout
+# One kernel serves the bf16, fp8 and MXFP4 images (S = 1, 2, 4; a 2-KiB chunk = 64 S k). Its waves
+# split the chunks of a 16-row group and each runs a DEPTH-deep register ring, so K picks the ring
+# case: waves with no chunk, fewer than DEPTH - 1 chunks, exactly DEPTH, DEPTH + 1 unevenly split.
+# (The MXFP4 cases are in test_fp4_decode_gpu.py.)
+_G16 = {}
+
+
+def _g16_data(fmt, N, K):
+    """weight (bf16: its tile-ordered image; fp8: image + scales), 16 rows of X, residual and the
+    fp32 products x w^T / rstd(x), built once per shape and left unchanged"""
+    if (fmt, N, K) not in _G16:
+        g = torch.Generator().manual_seed(N + K)
+        w = (torch.randn(N, K, generator=g) / math.sqrt(K)).to(torch.bfloat16).to(DEV)
+        x = (torch.randn(16, K, generator=g) * 2).to(torch.bfloat16).to(DEV)
+        res = torch.randn(16, N, generator=g).to(torch.bfloat16).to(DEV)
+        if fmt == "fp8":
+            q, s = ops.quantize_fp8(w)
+            wd, img = ops.dequantize_fp8(q, s), (ops.native().shuffle_decode_weight_fp8(q), s)
+        else:
+            wd, img = w.float(), ops.native().shuffle_decode_weight(w)
+        y = x.float() @ wd.t()
+        rstd = torch.rsqrt(x.float().pow(2).mean(-1, keepdim=True) + 1e-5)
+        _G16[(fmt, N, K)] = (img, x, res, y, rstd)
+    return _G16[(fmt, N, K)]
+
+
+def _g16_run(fmt, N, K, rows, mode):
+    """mode plain / plain_f32 (bf16 image only) / norm_res / pair on X rows `rows` -> (got, oracle)"""
+    img, x, res, y, rstd = _g16_data(fmt, N, K)
+    xs, rs, y, rstd = x[rows].contiguous(), res[rows].contiguous(), y[rows], rstd[rows]
+    act = ops.ACT_SWIGLU if mode == "pair" else 0
+    r, eps = (rs, 1e-5) if mode == "norm_res" else (None, 1e-5 if mode == "pair" else 0.0)
+    if fmt == "fp8":
+        got = ops.native().gemm_fp8(xs, None, img[0], img[1], None, act, None, r, eps, True)
+    else:
+        got = ops.native().gemm(xs, img, None, None, None, act, mode == "plain_f32", None, r, eps, True)
+    if mode == "pair":
+        want = torch.nn.functional.silu(y[:, :N // 2] * rstd) * (y[:, N // 2:] * rstd)
+    else:
+        want = y * rstd + rs.float() if mode == "norm_res" else y
+    return got, want
+
+
+def _g16_check(fmt, N, K, M, mode):
+    got, want = _g16_run(fmt, N, K, slice(0, M), mode)
+    assert got.dtype == (torch.float32 if mode == "plain_f32" else torch.bfloat16) and got.shape == want.shape
+    if mode == "plain_f32":
+        _close(got, want, rtol=1e-4, atol=1e-3)
+    else:
+        _close(got, want)
+
+
+@pytest.mark.parametrize("K", [128, 640, 2048, 2432])
+def test_gemv16_fp8_ring_edges(K):
+    """fp8 image, depth 4, 4 waves, 128 k per chunk: 1 chunk (three waves idle), 5 (1-2 per wave: the
+    ring never fills), 16 (exactly DEPTH each), 19 (4-5 per wave: one full turn plus a drain)."""
+    for M in (1, 16):
+        for mode in ("plain", "norm_res", "pair"):
+            _g16_check("fp8", 64, K, M, mode)
+
+
+@pytest.mark.parametrize("K,depth,waves", [(1024, 4, 4), (1024, 4, 8), (1024, 4, 16), (1088, 4, 4), (1088, 4, 8),
+                                           (1088, 4, 16), (1088, 6, 0), (1088, 8, 0)])
+def test_gemv16_bf16_ring_edges(K, depth, waves):
+    """bf16 image, 64 k per chunk: K = 1024 is 16 chunks (exactly DEPTH per wave at 4 waves, 2 at 8,
+    1 at 16), K = 1088 is 17 (4-5 per wave at 4 waves; 8 and 16 waves split unevenly below DEPTH - 1;
+    depth 6 and 8 never fill their ring). The route needs N / 16 >= 256 row groups: N = 4096, and
+    N = 8192 for the SwiGLU pair, which always runs depth 4 with 4 waves."""
+    with ops.tuning(gemv16_depth=depth, gemv16_waves=waves):
+        for M in (1, 16):
+            for mode in ("plain", "plain_f32", "norm_res"):
+                _g16_check("bf16", 4096, K, M, mode)
+            _g16_check("bf16", 8192, K, M, "pair")
+
+
+@pytest.mark.parametrize("fmt,N,K", [("bf16", 4096, 1024), ("fp8", 64, 128)])
+@pytest.mark.parametrize("mode", ["plain", "norm_res", "pair"])
+def test_gemv16_rows_do_not_depend_on_m(fmt, N, K, mode):
+    """row r of the 16-row result is bitwise the 1-row result of row r alone: the form is chosen by
+    the shape, and the MFMA rows past M repeat row M - 1"""
+    if fmt == "bf16" and mode == "pair":
+        N = 8192  # N / 32 >= 256 row-group pairs
+    y16, _ = _g16_run(fmt, N, K, slice(0, 16), mode)
+    for r in range(16):
+        y1, _ = _g16_run(fmt, N, K, slice(r, r + 1), mode)
+        assert torch.equal(y1.view(torch.int16), y16[r:r + 1].view(torch.int16)), f"row {r} differs"
+
+
+def _image_from_rule(rows, S):
+    """The documented image of row-major weight bytes `rows` [N, 16 K / (8 S)] (a 16-B unit = 8 S k
+    of one row): unit i = lane l = i & 63 of load h = (i >> 6) & 1 of tile i >> 7 = (G, c) holds row
+    16 G + (l & 15) at k = c KC + h KC / 2 + (l >> 4) 8 S, KC = 64 S. Returns (image, row, k)."""
+    N, per_row = rows.shape[0], rows.shape[1] // 16
+    nc = per_row * 8 * S // (64 * S)
+    i = torch.arange(N * per_row)
+    l, h, tile = i & 63, (i >> 6) & 1, i >> 7
+    row = 16 * (tile // nc) + (l & 15)
+    k = (tile % nc) * 64 * S + h * 32 * S + (l >> 4) * 8 * S
+    return rows.reshape(N, per_row, 16)[row, k // (8 * S)].reshape(N, per_row * 16), row, k
+
+
+@pytest.mark.parametrize("S", [1, 2, 4])
+def test_decode_weight_images_follow_the_s_rule(S):
+    N, K = 32, 512
+    w = (torch.randn(N, K, generator=torch.Generator().manual_seed(S)) * torch.logspace(-2, 2, N)[:, None]).to(torch.bfloat16)
+    C = ops.native()
+    if S == 1:
+        rows, got = w.view(torch.uint8), C.shuffle_decode_weight(w.to(DEV)).cpu().view(torch.uint8)
+    elif S == 2:
+        q, _ = ops.quantize_fp8(w.to(DEV))
+        rows, got = q.cpu(), C.shuffle_decode_weight_fp8(q).cpu()
+    else:
+        q, s = ops.quantize_mxfp4(w.to(DEV))
+        got, simg = (t.cpu() for t in C.shuffle_decode_weight_fp4(q, s))
+        rows, s = q.cpu(), s.cpu()
+    want, row, k = _image_from_rule(rows, S)
+    assert got.shape == want.shape and torch.equal(got, want)
+    if S == 4:
+        # scale word i = lane i & 63 of tile i >> 6: the scale bytes of that lane's loads h = 0 (low
+        # byte) and h = 1 (high byte) = the MX blocks k / 32 and k / 32 + 4 of its unit with h = 0
+        u = torch.arange(N * K // 64)
+        u = ((u >> 6) << 7) | (u & 63)
+        swant = torch.stack((s[row[u], k[u] // 32], s[row[u], k[u] // 32 + 4]), -1).reshape(N, K // 32)
+        assert torch.equal(simg, swant)
+
+
 # ------------------------------------------------------------------ fp8 K/V cache (config 5)
 def test_kv_store_fp8_matches_cpu_reference():
     torch.manual_seed(11)
