@@ -601,6 +601,152 @@ __device__ __forceinline__ void rope_chunk(const bf16_t* head, int dl, const Rop
   for (int k = 0; k < 8; ++k) out[k] = bf2f(f2bf(out[k]));
 }
 
+// rope_chunk on loaded registers: chunk xv rotated with its partner chunk yv by the table chunks
+// c / sn (lo: xv lies in the first half of the head), rounded to bf16 as the unfused rope kernel
+// stores it. rope_chunk and rope8 share rope_qkv_kernel's fma order: every site that rotates a row
+// appends the same bits.
+__device__ __forceinline__ uint4 rope8(const uint4& xv, const uint4& yv, const float4 (&c)[2], const float4 (&sn)[2],
+                                       bool lo, bool rot, float sign) {
+  if (!rot) return xv;
+  float x[8], y[8], o8[8];
+  unpack8(xv, x);
+  unpack8(yv, y);
+  const float cs[8] = {c[0].x, c[0].y, c[0].z, c[0].w, c[1].x, c[1].y, c[1].z, c[1].w};
+  const float sv[8] = {sn[0].x, sn[0].y, sn[0].z, sn[0].w, sn[1].x, sn[1].y, sn[1].z, sn[1].w};
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float t = sign * sv[e];
+    o8[e] = fmaf(x[e], cs[e], lo ? -(y[e] * t) : y[e] * t);
+  }
+  return pack8(o8);
+}
+
+// One (batch, kv head) row of a decode step: the keys [kbeg, len) it attends to (kv_start and the
+// window applied), the new token's slot and rotary position, its q | k | v row, and the cache row
+// (fp8 cache: byte rows and the per-slot scales)
+template <bool KV8>
+struct DecodeRow {
+  typedef typename std::conditional<KV8, unsigned char, bf16_t>::type cache_t;
+  int len, s_new, kbeg, pos;
+  const bf16_t* qkv;
+  cache_t *kbase, *vbase;  // [Smax, D]
+  float *ksb, *vsb;        // [SmaxP] (KV8)
+};
+template <int D, bool KV8>
+__device__ __forceinline__ DecodeRow<KV8> decode_row(const DecodeFusedArgs& a, int b, int hk) {
+  DecodeRow<KV8> r;
+  r.len = a.attn_len[b];
+  r.s_new = a.slot[b];
+  RT_ASSERT(r.len <= a.Smax && r.s_new >= 0 && r.s_new < a.Smax);
+  r.kbeg = a.kv_start ? a.kv_start[b] : 0;
+  if (a.window > 0) r.kbeg = max(r.kbeg, r.len - a.window);
+  r.pos = a.pos ? a.pos[b] : 0;
+  r.qkv = a.qkv + (long)b * a.ldq;
+  const long bh = (long)b * a.Hkv + hk;
+  r.kbase = (typename DecodeRow<KV8>::cache_t*)a.kc + bh * a.Smax * D;
+  r.vbase = (typename DecodeRow<KV8>::cache_t*)a.vc + bh * a.Smax * D;
+  r.ksb = KV8 ? a.ksc + bh * a.SmaxP : nullptr;
+  r.vsb = KV8 ? a.vsc + bh * a.SmaxP : nullptr;
+  return r;
+}
+
+// ---- the new token in the (g, r16) lane layout of the D = 128 decode kernels: lane group g holds
+// chunks 4 s + g (s < 4) of q and k_new, lane r16 chunk r16 of v_new ----
+struct NewToken {
+  uint4 q[4], k[4];  // rotated
+  uint4 v;
+};
+// Every q / k_new / v_new / rotary-table load is issued before any is used (one round trip). Chunk
+// 4 s + g's rotary partner (chunk ^ 8) is the lane's own chunk 4 (s ^ 2) + g, and its table offset
+// ((chunk & 7) * 8) depends on s & 1 only. Without tables the table loads read `any` (256 readable
+// bytes) instead: no branch between the load batches.
+__device__ __forceinline__ NewToken load_new_token(const bf16_t* qrow, const bf16_t* krow, const bf16_t* vrow,
+                                                   const float* cosT, const float* sinT, float sign, int pos,
+                                                   const void* any, int g, int r16) {
+  constexpr int D = 128;
+  const bool rot = cosT != nullptr;
+  uint4 qraw[4], kraw[4];
+#pragma unroll
+  for (int s2 = 0; s2 < 4; ++s2) {
+    qraw[s2] = *(const uint4*)(qrow + (4 * s2 + g) * 8);
+    kraw[s2] = *(const uint4*)(krow + (4 * s2 + g) * 8);
+  }
+  NewToken t;
+  t.v = *(const uint4*)(vrow + r16 * 8);
+  float4 cq[2][2], sq[2][2];
+  const float* ct = rot ? cosT + (long)pos * (D / 2) : (const float*)any;
+  const float* stb = rot ? sinT + (long)pos * (D / 2) : (const float*)any;
+#pragma unroll
+  for (int par = 0; par < 2; ++par) {
+    const int j0 = (4 * par + g) * 8;
+    cq[par][0] = *(const float4*)(ct + j0); cq[par][1] = *(const float4*)(ct + j0 + 4);
+    sq[par][0] = *(const float4*)(stb + j0); sq[par][1] = *(const float4*)(stb + j0 + 4);
+  }
+#pragma unroll
+  for (int s2 = 0; s2 < 4; ++s2) {
+    t.q[s2] = rope8(qraw[s2], qraw[s2 ^ 2], cq[s2 & 1], sq[s2 & 1], s2 < 2, rot, sign);
+    t.k[s2] = rope8(kraw[s2], kraw[s2 ^ 2], cq[s2 & 1], sq[s2 & 1], s2 < 2, rot, sign);
+  }
+  return t;
+}
+
+// scale of an fp8 cache row (e4m3fn: largest finite value 448) from its absolute maximum
+__device__ __forceinline__ float fp8_row_scale(float amax) { return amax > 0.f ? amax / 448.f : 1.f; }
+
+// fp8 cache: k_new / v_new quantised per (token, kv head). A step attends over the quantised values
+// too — exactly the bytes and scales later steps read from the cache. WIDEN: t.k / t.v are replaced
+// by the quantised values widened back to bf16 (unscaled), as the MFMA kernel's tiles hold them.
+struct NewTokenFp8 {
+  uint2 kq[4], vq;  // chunks 4 s + g of k_new, chunk r16 of v_new
+  float sk, sv;
+};
+template <bool WIDEN>
+__device__ __forceinline__ NewTokenFp8 quantise_new_token(NewToken& t) {
+  NewTokenFp8 n;
+  float amk = 0.f, amv = 0.f, f[8];
+#pragma unroll
+  for (int s2 = 0; s2 < 4; ++s2) {
+    unpack8(t.k[s2], f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) amk = fmaxf(amk, fabsf(f[e]));
+  }
+  amk = fmaxf(amk, __shfl_xor(amk, 16, 64));  // lane group g holds chunks 4 s + g
+  amk = fmaxf(amk, __shfl_xor(amk, 32, 64));
+  unpack8(t.v, f);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) amv = fmaxf(amv, fabsf(f[e]));
+#pragma unroll
+  for (int o2 = 1; o2 < 16; o2 <<= 1) amv = fmaxf(amv, __shfl_xor(amv, o2, 64));  // chunk r16
+  n.sk = fp8_row_scale(amk);
+  n.sv = fp8_row_scale(amv);
+  const float ik = 1.f / n.sk, iv = 1.f / n.sv;
+#pragma unroll
+  for (int s2 = 0; s2 < 4; ++s2) {
+    unpack8(t.k[s2], f);
+    n.kq[s2] = f32x8_to_fp8(f, ik);
+    if (WIDEN) t.k[s2] = __builtin_bit_cast(uint4, fp8x8_to_bf16(n.kq[s2].x, n.kq[s2].y));
+  }
+  unpack8(t.v, f);
+  n.vq = f32x8_to_fp8(f, iv);
+  if (WIDEN) t.v = __builtin_bit_cast(uint4, fp8x8_to_bf16(n.vq.x, n.vq.y));
+  return n;
+}
+
+// fp8 append by one wave: lane (g, 0) stores its 4 k chunks k-permuted (chunks 4 s + g at bytes
+// 32 g + 8 s), lane group 1 the v chunks, lane 0 the two scales
+__device__ __forceinline__ void append_new_token_fp8(const NewTokenFp8& n, unsigned char* kdst, unsigned char* vdst,
+                                                     float* ksc, float* vsc, int g, int r16) {
+  if (r16 == 0) {
+    *(uint4*)(kdst + 32 * g) = make_uint4(n.kq[0].x, n.kq[0].y, n.kq[1].x, n.kq[1].y);
+    *(uint4*)(kdst + 32 * g + 16) = make_uint4(n.kq[2].x, n.kq[2].y, n.kq[3].x, n.kq[3].y);
+  }
+  if (g == 1) *(uint2*)(vdst + r16 * 8) = n.vq;
+  if (g == 0 && r16 == 0) {
+    *ksc = n.sk;
+    *vsc = n.sv;
+  }
+}
+
 // One key chunk: CH = 4 waves x KPW keys x NK keys per lane. Loads of chunk j+1 are issued before
 // chunk j is consumed (two named register sets), softmax is online across chunks.
 template <int D, int NK>
@@ -759,6 +905,12 @@ __device__ __forceinline__ void walk_partition(const bf16_t* kbase, const bf16_t
   for (int gg = 0; gg < G; ++gg) lrow[gg] = wst[0][gg][1] + wst[1][gg][1] + wst[2][gg][1] + wst[3][gg][1];
 }
 
+// walk_partition's unnormalised O of (head gg, element d): the 4 waves' sums, added in wave order
+template <int D, int G>
+__device__ __forceinline__ float sum_waves4(const float (&red)[4 * G * D], int gg, int d) {
+  return red[(0 * G + gg) * D + d] + red[(1 * G + gg) * D + d] + red[(2 * G + gg) * D + d] + red[(3 * G + gg) * D + d];
+}
+
 // (M, L, O) <- merge((M, L, O), (mq, lq, oq)) of two unnormalised softmax partials (row maximum,
 // row sum, one output element). An empty partial (mq = -inf: its o was never written) is skipped.
 // Every merge over key partitions runs these operations in this order.
@@ -771,20 +923,75 @@ __device__ __forceinline__ void merge_partial(float& M, float& L, float& O, floa
   M = Mn;
 }
 
-// The last-arriving partition's merge of a row's NP published records {o[D], m, l} (agent-scope
-// loads; record q of the row at rec + q * stride): the normalised output element d.
-template <int D>
-__device__ __forceinline__ float merge_partitions(const float* rec, int stride, int NP, int d) {
-  float M = -INFINITY, L = 0.f, O = 0.f;
-#pragma unroll 4
-  for (int q = 0; q < NP; ++q) {
-    const float* r = rec + (long)q * stride;
-    const float mq = __hip_atomic_load(r + D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const float lq = __hip_atomic_load(r + D + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const float oq = __hip_atomic_load(r + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    merge_partial(M, L, O, mq, lq, oq);
+// (M, L, O) <- the merge of W waves' unnormalised states in LDS: wave q's row maximum and sum at
+// m[q * mls] / l[q * mls], its output element at o[q * os]. A wave without a tile holds m = -inf,
+// l = 0 and is skipped.
+template <int W>
+__device__ __forceinline__ void merge_waves(const float* m, const float* l, int mls, const float* o, int os, float& M,
+                                            float& L, float& O) {
+  M = -INFINITY;
+#pragma unroll
+  for (int q = 0; q < W; ++q) M = fmaxf(M, m[q * mls]);
+  L = 0.f;
+  O = 0.f;
+  if (M == -INFINITY) return;
+#pragma unroll
+  for (int q = 0; q < W; ++q) {
+    const float mq = m[q * mls];
+    if (mq == -INFINITY) continue;
+    const float f = exp2f(mq - M);
+    L += l[q * mls] * f;
+    O += o[q * os] * f;
   }
-  return L > 0.f ? O / L : 0.f;
+}
+
+// ---- Key partitions of one (batch, kv head) row handed from NP workgroups to the last of them.
+// The workspace holds one record {o[D], m, l} per (partition, query head): partition `part`'s
+// record of head h at rec + (part * G + h) * (D + 2). ----
+// element d of a record (unnormalised) and, with d = 0, its row maximum and sum
+template <int D>
+__device__ __forceinline__ void publish_partial(float* rec, int d, float O, float M, float L) {
+  __hip_atomic_store(rec + d, O, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (d == 0) {
+    __hip_atomic_store(rec + D, M, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(rec + D + 1, L, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+// Called by the whole workgroup after its publish_partial calls; true (to every thread) in the last
+// of the row's NP workgroups to arrive. Ordering, with no L2 writeback / invalidate fences
+// (cdna_hip_programming.md / MI355X_MICROARCH.md 'handoff-flag'): the records are write-through
+// (agent-scope) stores, every thread drains its own (vmcnt 0) before the barrier, so all of the
+// workgroup's payload is at L2 when thread 0 takes the relaxed ticket; the last arriver then reads
+// the records with agent-scope loads.
+__device__ __forceinline__ bool partition_arrive(unsigned* ticket, int NP) {
+  __shared__ int last;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned old = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = old == (unsigned)(NP - 1);
+  }
+  __syncthreads();
+  return last;
+}
+// The last arriver (NT threads): merges the row's NP records in partition order (merge_partial),
+// stores the normalised G x D outputs to orow and re-arms the ticket for the next launch
+template <int D, int G, int NT>
+__device__ __forceinline__ void merge_partitions_store(const float* rec, int NP, bf16_t* orow, unsigned* ticket) {
+  for (int e = threadIdx.x; e < G * D; e += NT) {
+    const int h = e / D, d = e % D;
+    float M = -INFINITY, L = 0.f, O = 0.f;
+#pragma unroll 4
+    for (int q = 0; q < NP; ++q) {
+      const float* r = rec + ((long)q * G + h) * (D + 2);
+      const float mq = __hip_atomic_load(r + D, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const float lq = __hip_atomic_load(r + D + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const float oq = __hip_atomic_load(r + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      merge_partial(M, L, O, mq, lq, oq);
+    }
+    orow[h * D + d] = f2bf(L > 0.f ? O / L : 0.f);
+  }
+  if (threadIdx.x == 0) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 template <int D, int G, int NK>
@@ -792,43 +999,35 @@ __global__ __launch_bounds__(256) void attn_decode_fused_kernel(DecodeFusedArgs 
   constexpr int LPK = D / 8, KPW = 64 / LPK;  // lanes per key, keys per wave-step
   __shared__ float red[4 * G * D];
   __shared__ float wst[4][G][2];
-  __shared__ int flag;
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int part = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
-  const int len = a.attn_len[b];
-  const int s_new = a.slot[b];
-  RT_ASSERT(len <= a.Smax && s_new >= 0 && s_new < a.Smax);
-  int kbeg = a.kv_start ? a.kv_start[b] : 0;
-  if (a.window > 0) kbeg = max(kbeg, len - a.window);
-  const int p0 = max(part * a.PS, kbeg), p1 = min((part + 1) * a.PS, len);
+  const DecodeRow<false> R = decode_row<D, false>(a, b, hk);
+  const int s_new = R.s_new;
+  const int p0 = max(part * a.PS, R.kbeg), p1 = min((part + 1) * a.PS, R.len);
   const int sub = lane / LPK, dl = lane % LPK;
-  const bf16_t* row = a.qkv + (long)b * a.ldq;
 
   float mrow[G], lrow[G];
   const bool active = p0 < p1;
   if (active) {
     const RopeTab rt{a.cosT, a.sinT, a.sign};
-    const int p = a.pos ? a.pos[b] : 0;
-    const bf16_t* kbase = a.kc + ((long)b * a.Hkv + hk) * a.Smax * D;
-    const bf16_t* vbase = a.vc + ((long)b * a.Hkv + hk) * a.Smax * D;
     const bool has_new = s_new >= p0 && s_new < p1;
     uint4 kp = make_uint4(0, 0, 0, 0), vp = kp;
     float qv[G][8];
     walk_partition<D, G, NK>(
-        kbase, vbase, p0, p1, a.kv_nt, qv, a.scale_log2, red, wst,
+        R.kbase, R.vbase, p0, p1, a.kv_nt, qv, a.scale_log2, red, wst,
         [&] {  // q rotated; the partition owning the new slot rotates k_new, appends k / v and keeps them
 #pragma unroll
-          for (int gg = 0; gg < G; ++gg) rope_chunk<D>(row + (long)(hk * G + gg) * D, dl, rt, p, qv[gg]);
+          for (int gg = 0; gg < G; ++gg) rope_chunk<D>(R.qkv + (long)(hk * G + gg) * D, dl, rt, R.pos, qv[gg]);
           if (has_new) {
             float kn[8], vn[8];
-            rope_chunk<D>(row + (long)(a.Hq + hk) * D, dl, rt, p, kn);
-            unpack8(*(const uint4*)(row + (long)(a.Hq + a.Hkv + hk) * D + dl * 8), vn);
+            rope_chunk<D>(R.qkv + (long)(a.Hq + hk) * D, dl, rt, R.pos, kn);
+            unpack8(*(const uint4*)(R.qkv + (long)(a.Hq + a.Hkv + hk) * D + dl * 8), vn);
             kp = pack8(kn);
             vp = pack8(vn);
             if (wid == 0 && sub == 0) {
-              *(uint4*)(a.kc + (((long)b * a.Hkv + hk) * a.Smax + s_new) * D + dl * 8) = kp;
-              *(uint4*)(a.vc + (((long)b * a.Hkv + hk) * a.Smax + s_new) * D + dl * 8) = vp;
+              *(uint4*)(R.kbase + (long)s_new * D + dl * 8) = kp;
+              *(uint4*)(R.vbase + (long)s_new * D + dl * 8) = vp;
             }
           }
         },
@@ -843,53 +1042,32 @@ __global__ __launch_bounds__(256) void attn_decode_fused_kernel(DecodeFusedArgs 
         },
         mrow, lrow);
   }
+  bf16_t* orow = a.o + (long)b * a.ldo + (long)hk * G * D;
 
   if (a.NP == 1) {
     for (int e = tid; e < G * D; e += 256) {
       const int gg = e / D, d = e % D;
       float ov = 0.f;
-      if (active && lrow[gg] > 0.f)
-        ov = (red[(0 * G + gg) * D + d] + red[(1 * G + gg) * D + d] + red[(2 * G + gg) * D + d] +
-              red[(3 * G + gg) * D + d]) / lrow[gg];
-      a.o[(long)b * a.ldo + (long)(hk * G + gg) * D + d] = f2bf(ov);
+      if (active && lrow[gg] > 0.f) ov = sum_waves4<D, G>(red, gg, d) / lrow[gg];
+      orow[e] = f2bf(ov);
     }
     return;
   }
 
-  // ---- publish the partial with write-through (agent-scope) stores, take a ticket; the last
-  // partition of (b, hk) merges with agent-scope loads. No L2 writeback / invalidate fences:
-  // cdna_hip_programming.md / MI355X_MICROARCH.md 'handoff-flag' (drained sc1 payload -> flag).
-  float* pp = a.part + (((long)b * a.Hkv + hk) * a.NP) * G * (D + 2);
-  float* outp = pp + (long)part * G * (D + 2);
+  // ---- publish the partial (an empty partition: m = -inf, skipped by the merge); the last
+  // partition of (b, hk) to arrive merges them all ----
+  const long bh = (long)b * a.Hkv + hk;
+  float* rec = a.part + bh * a.NP * G * (D + 2);
   for (int e = tid; e < G * D; e += 256) {
     const int gg = e / D, d = e % D;
-    if (active)
-      __hip_atomic_store(outp + gg * (D + 2) + d,
-                         red[(0 * G + gg) * D + d] + red[(1 * G + gg) * D + d] + red[(2 * G + gg) * D + d] +
-                             red[(3 * G + gg) * D + d],
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    float mq = -INFINITY, lq = 0.f;
+#pragma unroll
+    for (int g2 = 0; g2 < G; ++g2)
+      if (g2 == gg && active) { mq = mrow[g2]; lq = lrow[g2]; }
+    publish_partial<D>(rec + ((long)part * G + gg) * (D + 2), d, active ? sum_waves4<D, G>(red, gg, d) : 0.f, mq, lq);
   }
-  if (tid < G) {
-    __hip_atomic_store(outp + tid * (D + 2) + D, active ? mrow[tid] : -INFINITY, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(outp + tid * (D + 2) + D + 1, active ? lrow[tid] : 0.f, __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned old = __hip_atomic_fetch_add(a.tickets + (long)b * a.Hkv + hk, 1u, __ATOMIC_RELAXED,
-                                                __HIP_MEMORY_SCOPE_AGENT);
-    flag = (old == (unsigned)(a.NP - 1));
-  }
-  __syncthreads();
-  if (!flag) return;
-  for (int e = tid; e < G * D; e += 256) {
-    const int gg = e / D, d = e % D;
-    a.o[(long)b * a.ldo + (long)(hk * G + gg) * D + d] =
-        f2bf(merge_partitions<D>(pp + gg * (D + 2), G * (D + 2), a.NP, d));
-  }
-  if (tid == 0) __hip_atomic_store(a.tickets + (long)b * a.Hkv + hk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (!partition_arrive(a.tickets + bh, a.NP)) return;
+  merge_partitions_store<D, G, 256>(rec, a.NP, orow, a.tickets + bh);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -919,17 +1097,10 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_g1_fp8_kernel(DecodeFused
   const int w = (int)(threadIdx.x >> 6);
   const int bh = blockIdx.x;
   const int b = bh / a.Hkv, hk = bh % a.Hkv;
-  const int len = a.attn_len[b];
-  const int s_new = a.slot[b];
-  RT_ASSERT(len <= a.Smax && s_new >= 0 && s_new < a.Smax);
-  int kbeg = a.kv_start ? a.kv_start[b] : 0;
-  if (a.window > 0) kbeg = max(kbeg, len - a.window);
-  const int p = a.pos ? a.pos[b] : 0;
-  const bf16_t* row = a.qkv + (long)b * a.ldq;
-  const unsigned char* kbase = (const unsigned char*)a.kc + (long)bh * a.Smax * D;
-  const unsigned char* vbase = (const unsigned char*)a.vc + (long)bh * a.Smax * D;
-  const float* ksb = a.ksc + (long)bh * a.SmaxP;
-  const float* vsb = a.vsc + (long)bh * a.SmaxP;
+  const DecodeRow<true> R = decode_row<D, true>(a, b, hk);
+  const int len = R.len, s_new = R.s_new, kbeg = R.kbeg;
+  const unsigned char *kbase = R.kbase, *vbase = R.vbase;
+  const float *ksb = R.ksb, *vsb = R.vsb;
 
   struct Tile { uint4 k0, k1; uint2 v[4]; float ks, vs; };
   auto load = [&](Tile& T, int c0) {
@@ -949,95 +1120,23 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_g1_fp8_kernel(DecodeFused
   if (cf + 2 * ST < len) load(tc, cf + 2 * ST);
   if (cf + 3 * ST < len) load(td, cf + 3 * ST);
 
-  // ---- q / k_new / v_new (+ RoPE): lane group g holds chunks 4 s + g of q and k, chunk r of v
-  const bool rot = a.cosT != nullptr;
-  const bf16_t* qrow = row + (long)hk * D;
-  const bf16_t* krow = row + (long)(a.Hq + hk) * D;
-  const bf16_t* vrow = row + (long)(a.Hq + a.Hkv + hk) * D;
-  uint4 qraw[4], kraw[4];
-#pragma unroll
-  for (int s2 = 0; s2 < 4; ++s2) {
-    qraw[s2] = *(const uint4*)(qrow + (4 * s2 + g) * 8);
-    kraw[s2] = *(const uint4*)(krow + (4 * s2 + g) * 8);
-  }
-  const uint4 vx = *(const uint4*)(vrow + r * 8);
-  float4 cq[2][2], sq[2][2];
-  {
-    const float* ct = rot ? a.cosT + (long)p * (D / 2) : (const float*)row;
-    const float* stb = rot ? a.sinT + (long)p * (D / 2) : (const float*)row;
-#pragma unroll
-    for (int par = 0; par < 2; ++par) {
-      const int j0 = (4 * par + g) * 8;
-      cq[par][0] = *(const float4*)(ct + j0); cq[par][1] = *(const float4*)(ct + j0 + 4);
-      sq[par][0] = *(const float4*)(stb + j0); sq[par][1] = *(const float4*)(stb + j0 + 4);
-    }
-  }
-  auto rope8 = [&](const uint4& xv, const uint4& yv, const float4 (&c)[2], const float4 (&sn)[2], bool lo) -> uint4 {
-    if (!rot) return xv;
-    float x[8], y[8], o8[8];
-    unpack8(xv, x);
-    unpack8(yv, y);
-    const float cs[8] = {c[0].x, c[0].y, c[0].z, c[0].w, c[1].x, c[1].y, c[1].z, c[1].w};
-    const float sv[8] = {sn[0].x, sn[0].y, sn[0].z, sn[0].w, sn[1].x, sn[1].y, sn[1].z, sn[1].w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float t = a.sign * sv[e];
-      o8[e] = fmaf(x[e], cs[e], lo ? -(y[e] * t) : y[e] * t);  // = rope_qkv_kernel's rounding
-    }
-    return pack8(o8);
-  };
+  // ---- the new token: rotated, quantised, appended by wave 0; this step attends over its bytes ----
+  NewToken nt = load_new_token(R.qkv + (long)hk * D, R.qkv + (long)(a.Hq + hk) * D,
+                               R.qkv + (long)(a.Hq + a.Hkv + hk) * D, a.cosT, a.sinT, a.sign, R.pos, R.qkv, g, r);
   float q[32];  // element 32 s + 8 g + e at q[8 s + e], times scale * log2 e
-  uint4 knew[4];
 #pragma unroll
   for (int s2 = 0; s2 < 4; ++s2) {
     float f[8];
-    unpack8(rope8(qraw[s2], qraw[s2 ^ 2], cq[s2 & 1], sq[s2 & 1], s2 < 2), f);
+    unpack8(nt.q[s2], f);
 #pragma unroll
     for (int e = 0; e < 8; ++e) q[8 * s2 + e] = f[e] * a.scale_log2;
-    knew[s2] = rope8(kraw[s2], kraw[s2 ^ 2], cq[s2 & 1], sq[s2 & 1], s2 < 2);
   }
-  // quantise k_new / v_new (absmax / 448 per head row), as attn_decode_mfma_kernel<KV8>
-  uint2 kq[4], vq;
-  float sk_new, sv_new;
-  {
-    float amk = 0.f, amv = 0.f, f[8];
-#pragma unroll
-    for (int s2 = 0; s2 < 4; ++s2) {
-      unpack8(knew[s2], f);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) amk = fmaxf(amk, fabsf(f[e]));
-    }
-    amk = fmaxf(amk, __shfl_xor(amk, 16, 64));
-    amk = fmaxf(amk, __shfl_xor(amk, 32, 64));
-    unpack8(vx, f);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) amv = fmaxf(amv, fabsf(f[e]));
-#pragma unroll
-    for (int o2 = 1; o2 < 16; o2 <<= 1) amv = fmaxf(amv, __shfl_xor(amv, o2, 64));
-    sk_new = amk > 0.f ? amk / 448.f : 1.f;
-    sv_new = amv > 0.f ? amv / 448.f : 1.f;
-#pragma unroll
-    for (int s2 = 0; s2 < 4; ++s2) {
-      unpack8(knew[s2], f);
-      kq[s2] = f32x8_to_fp8(f, 1.f / sk_new);
-    }
-    unpack8(vx, f);
-    vq = f32x8_to_fp8(f, 1.f / sv_new);
-  }
+  const NewTokenFp8 nq = quantise_new_token<false>(nt);
+  const uint2 vq = nq.vq;
+  const float sk_new = nq.sk, sv_new = nq.sv;
   const bool has_new = s_new >= kbeg && s_new < len;
-  if (has_new && w == 0) {
-    unsigned char* kdst = (unsigned char*)a.kc + ((long)bh * a.Smax + s_new) * D;
-    unsigned char* vdst = (unsigned char*)a.vc + ((long)bh * a.Smax + s_new) * D;
-    if (r == 0) {
-      *(uint4*)(kdst + 32 * g) = make_uint4(kq[0].x, kq[0].y, kq[1].x, kq[1].y);
-      *(uint4*)(kdst + 32 * g + 16) = make_uint4(kq[2].x, kq[2].y, kq[3].x, kq[3].y);
-    }
-    if (g == 1) *(uint2*)(vdst + r * 8) = vq;
-    if (lane == 0) {
-      a.ksc[(long)bh * a.SmaxP + s_new] = sk_new;
-      a.vsc[(long)bh * a.SmaxP + s_new] = sv_new;
-    }
-  }
+  if (has_new && w == 0)
+    append_new_token_fp8(nq, R.kbase + (long)s_new * D, R.vbase + (long)s_new * D, R.ksb + s_new, R.vsb + s_new, g, r);
 
   float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   float m = -INFINITY, l = 0.f;
@@ -1048,7 +1147,7 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_g1_fp8_kernel(DecodeFused
     if (has_new && s_new >= c0 && s_new < c0 + 16) {  // this step's own bytes and scales
       if (min(c0 + r, len - 1) == s_new) {
 #pragma unroll
-        for (int s2 = 0; s2 < 4; ++s2) { kw[2 * s2] = kq[s2].x; kw[2 * s2 + 1] = kq[s2].y; }
+        for (int s2 = 0; s2 < 4; ++s2) { kw[2 * s2] = nq.kq[s2].x; kw[2 * s2 + 1] = nq.kq[s2].y; }
         ks = sk_new;
         vs = sv_new;
       }
@@ -1124,6 +1223,8 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_g1_fp8_kernel(DecodeFused
   }
   __syncthreads();
   if (w == 0 && g == 0) {
+    // not merge_waves: through it the compiler contracts all nine sums into fmas, where this copy
+    // compiles to a multiply and an add for L and two of the eight y (one output bit in 10^5 moves)
     float M = -INFINITY;
 #pragma unroll
     for (int q2 = 0; q2 < NW; ++q2) M = fmaxf(M, mrg[q2][0]);
@@ -1145,7 +1246,8 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_g1_fp8_kernel(DecodeFused
 }
 
 // ---------------------------------------------------------------------------------------------
-// Fused decode step on MFMA (large batch: B * Hkv >= 256, one partition per (batch, kv head))
+// Fused decode step on MFMA (large batch: B * Hkv >= tuning().decode_mw_bh = 320, one partition per
+// (batch, kv head))
 // ---------------------------------------------------------------------------------------------
 // At batch 256 the decode attention of a layer streams ~250 MB of K/V (256 x 8 kv-heads x ~240
 // keys x 512 B); the VALU kernel above spends ~120 instructions per key-lane on dot products,
@@ -1167,7 +1269,7 @@ __global__ __launch_bounds__(64 * NW) void attn_decode_g1_fp8_kernel(DecodeFused
 // k_new / v_new from registers. Measured at batch 256 (Mistral-7B, 174..301 keys): 51 us per
 // layer vs 80 us for the VALU kernel (profiles/decode_attn_r2_mfma.log).
 //
-// W > 1 (small batch, B * Hkv < 256 — the batch-1 RAG answer path): W waves share one (batch, kv
+// W > 1 (small batch, B * Hkv below that — the batch-1 RAG answer path): W waves share one (batch, kv
 // head); wave w takes the 16-key tiles w, w + W, w + 2W, ... (its first two tiles' loads issued
 // with the prologue's), and the W partial (m, l, O) states merge through LDS in the same launch —
 // no cross-workgroup partition combine, so a layer's attention is one memory round trip plus a
@@ -1230,23 +1332,14 @@ __global__ __launch_bounds__(64 * W) void attn_decode_mfma_kernel(DecodeFusedArg
   const int NP = W > 1 ? max(a.NP, 1) : 1;
   const int part = blockIdx.x % NP, bh = blockIdx.x / NP;
   const int b = bh / a.Hkv, hk = bh % a.Hkv;
-  const int len_row = a.attn_len[b];
-  const int s_new = a.slot[b];
-  RT_ASSERT(len_row <= a.Smax && s_new >= 0 && s_new < a.Smax);
-  int kbeg = a.kv_start ? a.kv_start[b] : 0;
-  if (a.window > 0) kbeg = max(kbeg, len_row - a.window);
+  const DecodeRow<KV8> R = decode_row<D, KV8>(a, b, hk);
+  const int s_new = R.s_new;
   // this workgroup's keys [kbeg, len): the whole row, or partition `part` of it
-  const int len = NP > 1 ? min(len_row, (part + 1) * a.PS) : len_row;
-  if (NP > 1) kbeg = max(kbeg, part * a.PS);
-  const int p = a.pos ? a.pos[b] : 0;
-  const bf16_t* row = a.qkv + (long)b * a.ldq;
-  const bf16_t* kbase = a.kc + ((long)b * a.Hkv + hk) * a.Smax * D;
-  const bf16_t* vbase = a.vc + ((long)b * a.Hkv + hk) * a.Smax * D;
-  // fp8 cache: byte rows of D, scales per slot
-  const unsigned char* kbase8 = (const unsigned char*)a.kc + ((long)b * a.Hkv + hk) * a.Smax * D;
-  const unsigned char* vbase8 = (const unsigned char*)a.vc + ((long)b * a.Hkv + hk) * a.Smax * D;
-  const float* ksb = KV8 ? a.ksc + ((long)b * a.Hkv + hk) * a.SmaxP : nullptr;
-  const float* vsb = KV8 ? a.vsc + ((long)b * a.Hkv + hk) * a.SmaxP : nullptr;
+  const int len = NP > 1 ? min(R.len, (part + 1) * a.PS) : R.len;
+  const int kbeg = NP > 1 ? max(R.kbeg, part * a.PS) : R.kbeg;
+  const bf16_t* row = R.qkv;
+  const auto kbase = R.kbase, vbase = R.vbase;  // bf16 rows of D elements; fp8: byte rows, scales per slot
+  const float *ksb = R.ksb, *vsb = R.vsb;
 
   // tile of 16 keys from c0 (32 registers per set: two sets keep every wave of a batch-256 layer
   // resident, 3 per SIMD): K fragments k[s] = K[c0 + r16][32 s + 8 g ..] (A operand of S^T);
@@ -1260,10 +1353,10 @@ __global__ __launch_bounds__(64 * W) void attn_decode_mfma_kernel(DecodeFusedArg
   auto load = [&](Tile& T, int c0) {
     const long keyk = min(c0 + r16, len - 1);
     if constexpr (KV8) {
-      T.k8[0] = load_nt16(kbase8 + keyk * D + 32 * g);
-      T.k8[1] = load_nt16(kbase8 + keyk * D + 32 * g + 16);
+      T.k8[0] = load_nt16(kbase + keyk * D + 32 * g);
+      T.k8[1] = load_nt16(kbase + keyk * D + 32 * g + 16);
 #pragma unroll
-      for (int i = 0; i < 4; ++i) T.v8[i] = load_nt8(vbase8 + (long)min(c0 + 4 * i + g, len - 1) * D + 8 * r16);
+      for (int i = 0; i < 4; ++i) T.v8[i] = load_nt8(vbase + (long)min(c0 + 4 * i + g, len - 1) * D + 8 * r16);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int key = min(c0 + 4 * g + i, len - 1);
@@ -1294,10 +1387,7 @@ __global__ __launch_bounds__(64 * W) void attn_decode_mfma_kernel(DecodeFusedArg
   if ((W > 1 || DEEP8) && cfirst + cstep < len) load(tb, cfirst + cstep);
   if ((W > 1 || DEEP8) && cfirst + 2 * cstep < len) load(tc, cfirst + 2 * cstep);
 
-  // ---- q / k_new / v_new and the rotary tables, all loads at once. D = 128: chunk 4 s + g's
-  // rotary partner (chunk ^ 8) is the lane's own chunk 4 (s ^ 2) + g, its table offset
-  // ((chunk & 7) * 8) depends on s & 1 only ----
-  const bool rot = a.cosT != nullptr;
+  // ---- q / k_new / v_new (load_new_token: one round trip behind the first tiles' loads) ----
   const bool has_new = s_new >= kbeg && s_new < len;
   const bf16_t* qrow = row + (long)min(hk * G + r16, a.Hq - 1) * D;
   const bf16_t* krow = row + (long)(a.Hq + hk) * D;
@@ -1317,107 +1407,27 @@ __global__ __launch_bounds__(64 * W) void attn_decode_mfma_kernel(DecodeFusedArg
     krow = qkv_st + G * D;
     vrow = qkv_st + (G + 1) * D;
   }
-  uint4 qraw[DS], kraw[DS];
+  NewToken nt = load_new_token(qrow, krow, vrow, a.cosT, a.sinT, a.sign, R.pos, row, g, r16);
+  bf16x8 qf[DS];  // B operand of S^T = K·Q^T: Q[head r16][32 s + 8 g ..]
 #pragma unroll
-  for (int s2 = 0; s2 < DS; ++s2) {
-    qraw[s2] = *(const uint4*)(qrow + (4 * s2 + g) * 8);
-    kraw[s2] = *(const uint4*)(krow + (4 * s2 + g) * 8);
-  }
-  const uint4 vx = *(const uint4*)(vrow + r16 * 8);
-  float4 cq[2][2], sq[2][2];
-  {
-    // unconditional (no branch between load batches): without tables read the qkv row
-    const float* ct = rot ? a.cosT + (long)p * (D / 2) : (const float*)row;
-    const float* stb = rot ? a.sinT + (long)p * (D / 2) : (const float*)row;
-#pragma unroll
-    for (int par = 0; par < 2; ++par) {
-      const int j0 = (4 * par + g) * 8;
-      cq[par][0] = *(const float4*)(ct + j0); cq[par][1] = *(const float4*)(ct + j0 + 4);
-      sq[par][0] = *(const float4*)(stb + j0); sq[par][1] = *(const float4*)(stb + j0 + 4);
-    }
-  }
-  // x rotated with partner y: lo half (chunk < 8) x c - y s', hi half x c + y s' (s' = sign sin),
-  // rounded to bf16 as the unfused rope kernel stores it
-  auto rope8 = [&](const uint4& xv, const uint4& yv, const float4 (&c)[2], const float4 (&sn)[2], bool lo) -> uint4 {
-    if (!rot) return xv;
-    float x[8], y[8], o8[8];
-    unpack8(xv, x);
-    unpack8(yv, y);
-    const float cs[8] = {c[0].x, c[0].y, c[0].z, c[0].w, c[1].x, c[1].y, c[1].z, c[1].w};
-    const float sv[8] = {sn[0].x, sn[0].y, sn[0].z, sn[0].w, sn[1].x, sn[1].y, sn[1].z, sn[1].w};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float t = a.sign * sv[e];
-      o8[e] = fmaf(x[e], cs[e], lo ? -(y[e] * t) : y[e] * t);  // = rope_qkv_kernel's rounding
-    }
-    return pack8(o8);
-  };
-  bf16x8 qf[DS];   // B operand of S^T = K·Q^T: Q[head r16][32 s + 8 g ..]
-  uint4 knew[DS];  // rotated k_new chunks 4 s + g (the lane's K-fragment chunks)
-#pragma unroll
-  for (int s2 = 0; s2 < DS; ++s2) {
-    const uint4 qv = rope8(qraw[s2], qraw[s2 ^ 2], cq[s2 & 1], sq[s2 & 1], s2 < 2);
-    qf[s2] = __builtin_bit_cast(bf16x8, r16 < G ? qv : make_uint4(0, 0, 0, 0));
-    knew[s2] = rope8(kraw[s2], kraw[s2 ^ 2], cq[s2 & 1], sq[s2 & 1], s2 < 2);
-  }
+  for (int s2 = 0; s2 < DS; ++s2) qf[s2] = __builtin_bit_cast(bf16x8, r16 < G ? nt.q[s2] : make_uint4(0, 0, 0, 0));
   stamp(1);  // q / k_new / v_new / tables and the first tiles landed, RoPE done
-  // fp8 cache: quantise k_new / v_new per (token, kv head) (absmax / 448); this step attends over
-  // the quantised values too (knew / vxq hold them widened back to bf16, sk / sv their scales), so
-  // the step sees exactly what later steps read from the cache
-  uint4 vxq = vx;
+  // cache append by wave 0; the walk substitutes nt.k / nt.v at the new slot. fp8: quantised first, and
+  // nt.k / nt.v then hold the quantised values (sk_new / sv_new their scales). bf16: lane (g, 0) stores its 4 k chunks, lane group 1 the v chunks
   float sk_new = 1.f, sv_new = 1.f;
-  uint2 kq[DS], vq = make_uint2(0, 0);
   if constexpr (KV8) {
-    float amk = 0.f, amv = 0.f, f[8];
+    const NewTokenFp8 nq = quantise_new_token<true>(nt);
+    sk_new = nq.sk;
+    sv_new = nq.sv;
+    if (has_new && w == 0)
+      append_new_token_fp8(nq, R.kbase + (long)s_new * D, R.vbase + (long)s_new * D, R.ksb + s_new, R.vsb + s_new, g,
+                           r16);
+  } else if (has_new && w == 0) {
+    if (r16 == 0) {
 #pragma unroll
-    for (int s2 = 0; s2 < DS; ++s2) {
-      unpack8(knew[s2], f);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) amk = fmaxf(amk, fabsf(f[e]));
+      for (int s2 = 0; s2 < DS; ++s2) *(uint4*)(R.kbase + (long)s_new * D + (4 * s2 + g) * 8) = nt.k[s2];
     }
-    amk = fmaxf(amk, __shfl_xor(amk, 16, 64));  // lane group g holds chunks 4 s + g
-    amk = fmaxf(amk, __shfl_xor(amk, 32, 64));
-    unpack8(vx, f);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) amv = fmaxf(amv, fabsf(f[e]));
-#pragma unroll
-    for (int o2 = 1; o2 < 16; o2 <<= 1) amv = fmaxf(amv, __shfl_xor(amv, o2, 64));  // chunk r16
-    sk_new = amk > 0.f ? amk / 448.f : 1.f;
-    sv_new = amv > 0.f ? amv / 448.f : 1.f;
-    const float ik = 1.f / sk_new, iv = 1.f / sv_new;
-#pragma unroll
-    for (int s2 = 0; s2 < DS; ++s2) {
-      unpack8(knew[s2], f);
-      kq[s2] = f32x8_to_fp8(f, ik);
-      knew[s2] = __builtin_bit_cast(uint4, fp8x8_to_bf16(kq[s2].x, kq[s2].y));
-    }
-    unpack8(vx, f);
-    vq = f32x8_to_fp8(f, iv);
-    vxq = __builtin_bit_cast(uint4, fp8x8_to_bf16(vq.x, vq.y));
-  }
-  // cache append: lane (g, 0) stores its 4 k chunks 4 s + g, lane group 1 the v chunks (wave 0)
-  if (has_new && w == 0) {
-    if constexpr (KV8) {
-      unsigned char* kdst = (unsigned char*)a.kc + (((long)b * a.Hkv + hk) * a.Smax + s_new) * D;
-      unsigned char* vdst = (unsigned char*)a.vc + (((long)b * a.Hkv + hk) * a.Smax + s_new) * D;
-      if (r16 == 0) {  // k-permuted: chunks 4 s + g at bytes 32 g + 8 s
-        *(uint4*)(kdst + 32 * g) = make_uint4(kq[0].x, kq[0].y, kq[1].x, kq[1].y);
-        *(uint4*)(kdst + 32 * g + 16) = make_uint4(kq[2].x, kq[2].y, kq[3].x, kq[3].y);
-      }
-      if (g == 1) *(uint2*)(vdst + r16 * 8) = vq;
-      if (lane == 0) {
-        a.ksc[((long)b * a.Hkv + hk) * a.SmaxP + s_new] = sk_new;
-        a.vsc[((long)b * a.Hkv + hk) * a.SmaxP + s_new] = sv_new;
-      }
-    } else {
-      bf16_t* kdst = a.kc + (((long)b * a.Hkv + hk) * a.Smax + s_new) * D;
-      bf16_t* vdst = a.vc + (((long)b * a.Hkv + hk) * a.Smax + s_new) * D;
-      if (r16 == 0) {
-#pragma unroll
-        for (int s2 = 0; s2 < DS; ++s2) *(uint4*)(kdst + (4 * s2 + g) * 8) = knew[s2];
-      }
-      if (g == 1) *(uint4*)(vdst + r16 * 8) = vx;
-    }
+    if (g == 1) *(uint4*)(R.vbase + (long)s_new * D + r16 * 8) = nt.v;
   }
 
   f32x4 o[DT];
@@ -1454,11 +1464,11 @@ __global__ __launch_bounds__(64 * W) void attn_decode_mfma_kernel(DecodeFusedArg
     if (has_new && s_new >= c0 && s_new < c0 + 16) {
       if (min(c0 + r16, len - 1) == s_new) {
 #pragma unroll
-        for (int s2 = 0; s2 < DS; ++s2) kf[s2] = knew[s2];
+        for (int s2 = 0; s2 < DS; ++s2) kf[s2] = nt.k[s2];
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        if (min(c0 + 4 * i + g, len - 1) == s_new) vf[i] = vxq;
+        if (min(c0 + 4 * i + g, len - 1) == s_new) vf[i] = nt.v;
         if (KV8 && c0 + 4 * g + i == s_new) {  // this step's own scales (the prefetched ones may be stale)
           ks[i] = sk_new;
           vs[i] = sv_new;
@@ -1550,51 +1560,18 @@ __global__ __launch_bounds__(64 * W) void attn_decode_mfma_kernel(DecodeFusedArg
       }
     }
     __syncthreads();
-    float* pp = NP > 1 ? a.part + (long)bh * NP * G * (D + 2) : nullptr;
+    float* rec = NP > 1 ? a.part + (long)bh * NP * G * (D + 2) : nullptr;
+    bf16_t* orow = a.o + (long)b * a.ldo + (long)hk * G * D;
     for (int e = threadIdx.x; e < G * D; e += 64 * W) {
       const int h = e / D, d = e % D;
-      float M = -INFINITY;
-#pragma unroll
-      for (int q = 0; q < W; ++q) M = fmaxf(M, mst[q][h]);
-      float L = 0.f, O = 0.f;
-      if (M != -INFINITY) {
-#pragma unroll
-        for (int q = 0; q < W; ++q) {
-          const float mq = mst[q][h];
-          if (mq == -INFINITY) continue;
-          const float f = exp2f(mq - M);
-          L += lst[q][h] * f;
-          O += ost[q][h][d] * f;
-        }
-      }
-      if (NP > 1) {  // publish the unnormalised partial (write-through stores)
-        float* r = pp + ((long)part * G + h) * (D + 2);
-        __hip_atomic_store(r + d, O, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (d == 0) {
-          __hip_atomic_store(r + D, M, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          __hip_atomic_store(r + D + 1, L, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      } else {
-        a.o[(long)b * a.ldo + (long)(hk * G + h) * D + d] = f2bf(L > 0.f ? O / L : 0.f);
-      }
+      float M, L, O;
+      merge_waves<W>(&mst[0][h], &lst[0][h], 16, &ost[0][h][d], G * D, M, L, O);
+      if (NP > 1) publish_partial<D>(rec + ((long)part * G + h) * (D + 2), d, O, M, L);
+      else orow[e] = f2bf(L > 0.f ? O / L : 0.f);
     }
-    if (NP > 1) {
-      // drained payload -> ticket (handoff-flag); the row's last partition merges all NP records
-      __shared__ int last_flag;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        const unsigned old = __hip_atomic_fetch_add(a.tickets + bh, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last_flag = old == (unsigned)(NP - 1);
-      }
-      __syncthreads();
-      if (!last_flag) return;
-      for (int e = threadIdx.x; e < G * D; e += 64 * W) {
-        const int h = e / D, d = e % D;
-        a.o[(long)b * a.ldo + (long)(hk * G + h) * D + d] =
-            f2bf(merge_partitions<D>(pp + h * (D + 2), G * (D + 2), NP, d));
-      }
-      if (threadIdx.x == 0) __hip_atomic_store(a.tickets + bh, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (NP > 1) {  // the row's last partition to arrive merges all NP records
+      if (!partition_arrive(a.tickets + bh, NP)) return;
+      merge_partitions_store<D, G, 64 * W>(rec, NP, orow, a.tickets + bh);
     }
     stamp(3);
   }
@@ -1829,20 +1806,8 @@ __global__ __launch_bounds__(64 * W) void attn_verify_mfma_kernel(VerifyArgs a) 
   for (int e = tid; e < 16 * D; e += 64 * W) {
     const int h = e / D, d = e % D;
     if (rbase + h >= R) continue;
-    float M = -INFINITY;
-#pragma unroll
-    for (int q = 0; q < W; ++q) M = fmaxf(M, mst[q][h]);
-    float L = 0.f, O = 0.f;
-    if (M != -INFINITY) {
-#pragma unroll
-      for (int q = 0; q < W; ++q) {
-        const float mq = mst[q][h];
-        if (mq == -INFINITY) continue;
-        const float f = exp2f(mq - M);
-        L += lst[q][h] * f;
-        O += ost[(q * 16 + h) * D + d] * f;
-      }
-    }
+    float M, L, O;
+    merge_waves<W>(&mst[0][h], &lst[0][h], 16, ost + h * D + d, 16 * D, M, L, O);
     const int j = (rbase + h) >> a.qshift, hq = (rbase + h) & (Q - 1);
     a.o[(row0 + j) * a.ldo + (long)(hk * Q + hq) * D + d] = f2bf(L > 0.f ? O / L : 0.f);
   }
@@ -1934,9 +1899,7 @@ __global__ __launch_bounds__(256) void attn_verify_valu_kernel(VerifyArgs a) {
       const int e = tid + 256 * x;
       if (e >= G * D) continue;
       const int gg = e / D, d = e % D;
-      const float osum = active ? red[(0 * G + gg) * D + d] + red[(1 * G + gg) * D + d] + red[(2 * G + gg) * D + d] +
-                                      red[(3 * G + gg) * D + d]
-                                : 0.f;
+      const float osum = active ? sum_waves4<D, G>(red, gg, d) : 0.f;
       float mq = -INFINITY, lq = 0.f;
 #pragma unroll
       for (int g2 = 0; g2 < G; ++g2)
@@ -1960,6 +1923,29 @@ __global__ __launch_bounds__(256) void attn_verify_valu_kernel(VerifyArgs a) {
   }
 }
 
+// Launcher dispatch on the query heads per kv head (1, 2, 4, 8) and on (head_dim, heads per kv
+// head): f(std::integral_constant...) runs for the matching instantiation; false if there is none
+template <int N> using ic = std::integral_constant<int, N>;
+template <class F>
+static bool dispatch_g(int G, F&& f) {
+  switch (G) {
+    case 1: f(ic<1>{}); return true;
+    case 2: f(ic<2>{}); return true;
+    case 4: f(ic<4>{}); return true;
+    case 8: f(ic<8>{}); return true;
+    default: return false;
+  }
+}
+template <class F>
+static bool dispatch_dg(int D, int G, F&& f) {
+  switch (D) {
+    case 32: return dispatch_g(G, [&](auto g) { f(ic<32>{}, g); });
+    case 64: return dispatch_g(G, [&](auto g) { f(ic<64>{}, g); });
+    case 128: return dispatch_g(G, [&](auto g) { f(ic<128>{}, g); });
+    default: return false;
+  }
+}
+
 extern "C" int rt_attn_verify(const void* qkv, long ldq, void* kc, void* vc, int Smax, const int* slot0,
                               const int* len0, const int* kv_start, const int* pos0, const float* cosT,
                               const float* sinT, float sign, int window, void* o, long ldo, int B, int G, int Hq,
@@ -1980,12 +1966,9 @@ extern "C" int rt_attn_verify(const void* qkv, long ldq, void* kc, void* vc, int
     if (PS <= 0 || PS % (4 * (64 / (D / 8)) * 4) != 0) return -1;
     a.PS = PS; a.NP = (Smax + PS - 1) / PS;
     dim3 vgrid((unsigned)G, (unsigned)Hkv, (unsigned)B);
-    switch (Q) {
-      case 1: hipLaunchKernelGGL((attn_verify_valu_kernel<64, 1, 4>), vgrid, dim3(256), 0, stream, a); break;
-      case 2: hipLaunchKernelGGL((attn_verify_valu_kernel<64, 2, 4>), vgrid, dim3(256), 0, stream, a); break;
-      case 4: hipLaunchKernelGGL((attn_verify_valu_kernel<64, 4, 4>), vgrid, dim3(256), 0, stream, a); break;
-      default: hipLaunchKernelGGL((attn_verify_valu_kernel<64, 8, 4>), vgrid, dim3(256), 0, stream, a); break;
-    }
+    dispatch_g(Q, [&](auto q) {
+      hipLaunchKernelGGL((attn_verify_valu_kernel<64, decltype(q)::value, 4>), vgrid, dim3(256), 0, stream, a);
+    });
     RT_LAUNCH_CHECK();
     return 0;
   }
@@ -2453,18 +2436,17 @@ extern "C" int rt_attn_decode(const void* q, long ldq, const void* kc, const voi
   if (B == 0) return 0;
   dim3 grid(NP, Hkv, B), block(256);
   const size_t shm = (size_t)(G * PS + 4 * G * D) * sizeof(float);
-#define DEC_CASE(DD, GG)                                                                      \
-  if (D == DD && G == GG) {                                                                   \
-    hipLaunchKernelGGL((attn_decode_kernel<DD, GG>), grid, block, shm, stream, a);            \
-    hipLaunchKernelGGL((attn_decode_combine_kernel<DD, GG>), dim3(Hkv, B), dim3(256), 0, stream, a); \
-    RT_LAUNCH_CHECK();                                                                        \
-    return 0;                                                                                 \
-  }
-  DEC_CASE(128, 1) DEC_CASE(128, 2) DEC_CASE(128, 4) DEC_CASE(128, 8)
-  DEC_CASE(64, 1) DEC_CASE(64, 2) DEC_CASE(64, 4) DEC_CASE(64, 8)
-  DEC_CASE(32, 1)
-#undef DEC_CASE
-  return -1;
+  if (D == 32 && G != 1) return -1;
+  const bool ok = dispatch_dg(D, G, [&](auto d, auto g) {
+    constexpr int DD = decltype(d)::value, GG = decltype(g)::value;
+    if constexpr (DD != 32 || GG == 1) {
+      hipLaunchKernelGGL((attn_decode_kernel<DD, GG>), grid, block, shm, stream, a);
+      hipLaunchKernelGGL((attn_decode_combine_kernel<DD, GG>), dim3(Hkv, B), dim3(256), 0, stream, a);
+    }
+  });
+  if (!ok) return -1;
+  RT_LAUNCH_CHECK();
+  return 0;
 }
 
 // keys per chunk of the fused kernel: 4 waves x (64 / (D/8)) keys per step x NK (= 4)
@@ -2514,7 +2496,7 @@ __global__ __launch_bounds__(256) void kv_store_fp8_kernel(const bf16_t* __restr
   for (int e = 0; e < 8; ++e) am = fmaxf(am, fabsf(f[e]));
 #pragma unroll
   for (int o2 = 1; o2 < 16; o2 <<= 1) am = fmaxf(am, __shfl_xor(am, o2, 16));
-  const float sc = am > 0.f ? am / 448.f : 1.f;
+  const float sc = fp8_row_scale(am);
   const uint2 q = f32x8_to_fp8(f, 1.f / sc);
   const long base = (((long)b * Hkv + hk) * Smax + s) * D;
   if (kv == 0) *(uint2*)(kc + base + 32 * (c & 3) + 8 * (c >> 2)) = q;
@@ -2535,7 +2517,9 @@ extern "C" int rt_kv_store_fp8(const void* qkv, long ldq, void* kc, void* vc, fl
 }
 
 // attn_decode_mfma_kernel<G, W, KV8> on `blocks` workgroups of W waves; the caller has checked G
-// (1, 2, 4, 8; 16 exists only for the one-wave bf16 form, which rt_attn_decode_mfma_ok alone admits)
+// (1, 2, 4, 8; 16 exists only for the one-wave bf16 form, which rt_attn_decode_mfma_ok alone admits).
+// B * Hkv picks W: 8 below 256 pairs, 4 from 256 up to the one-wave threshold (tuning().decode_mw_bh,
+// 320: the test shape (32, 64, 8, 128, 200) with its 256 pairs runs W = 4), 1 above
 template <int W, bool KV8>
 static void launch_decode_mfma(int G, int blocks, const DecodeFusedArgs& a, hipStream_t stream) {
   const dim3 grid((unsigned)blocks), block(64 * W);
@@ -2545,12 +2529,9 @@ static void launch_decode_mfma(int G, int blocks, const DecodeFusedArgs& a, hipS
       return;
     }
   }
-  switch (G) {
-    case 1: hipLaunchKernelGGL((attn_decode_mfma_kernel<1, W, KV8>), grid, block, 0, stream, a); break;
-    case 2: hipLaunchKernelGGL((attn_decode_mfma_kernel<2, W, KV8>), grid, block, 0, stream, a); break;
-    case 4: hipLaunchKernelGGL((attn_decode_mfma_kernel<4, W, KV8>), grid, block, 0, stream, a); break;
-    default: hipLaunchKernelGGL((attn_decode_mfma_kernel<8, W, KV8>), grid, block, 0, stream, a); break;
-  }
+  dispatch_g(G, [&](auto g) {
+    hipLaunchKernelGGL((attn_decode_mfma_kernel<decltype(g)::value, W, KV8>), grid, block, 0, stream, a);
+  });
 }
 
 extern "C" int rt_attn_decode_fused(const void* qkv, long ldq, void* kc, void* vc, int Smax, const int* slot,
@@ -2615,17 +2596,12 @@ extern "C" int rt_attn_decode_fused(const void* qkv, long ldq, void* kc, void* v
   constexpr int NK = 4;  // keys per lane per chunk; PS must be a multiple of the chunk
   if (PS % (4 * (64 / (D / 8)) * NK) != 0) return -1;
   dim3 grid(NP, Hkv, B), block(256);
-#define DF_CASE(DD, GG)                                                                       \
-  if (D == DD && G == GG) {                                                                   \
-    hipLaunchKernelGGL((attn_decode_fused_kernel<DD, GG, NK>), grid, block, 0, stream, a);    \
-    RT_LAUNCH_CHECK();                                                                        \
-    return 0;                                                                                 \
-  }
-#define DF_G(DD) DF_CASE(DD, 1) DF_CASE(DD, 2) DF_CASE(DD, 4) DF_CASE(DD, 8)
-  DF_G(128) DF_G(64) DF_G(32)
-#undef DF_G
-#undef DF_CASE
-  return -1;
+  const bool ok = dispatch_dg(D, G, [&](auto d, auto g) {
+    hipLaunchKernelGGL((attn_decode_fused_kernel<decltype(d)::value, decltype(g)::value, NK>), grid, block, 0, stream, a);
+  });
+  if (!ok) return -1;
+  RT_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int rt_rope_qkv(void* qkv, long ld, const int* pos, const float* cosT, const float* sinT, int T, int S,

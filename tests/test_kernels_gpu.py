@@ -1,4 +1,5 @@
 """Numerics of every HIP kernel against the plain-PyTorch fp32 reference of the same op."""
+import contextlib
 import math
 
 import pytest
@@ -792,7 +793,10 @@ def test_pool_topk_ivf_gae():
                                                         # kernel over key partitions merged by the last arriver
                                                         (2, 32, 8, 128, 1500, True, 0), (1, 32, 8, 128, 4096, True, 0),
                                                         (1, 32, 8, 128, 8200, True, 4096), (2, 40, 40, 128, 2100, True, 0),
-                                                        # B * Hkv >= 256: the MFMA kernel (G = 4, 8, 1)
+                                                        # B * Hkv >= 256, below and at the one-wave threshold
+                                                        # (decode_mw_bh = 320): the MFMA kernel at 1 wave
+                                                        # (320 pairs, G = 4) and at 4 waves (256 pairs, G = 8
+                                                        # and G = 1)
                                                         (40, 32, 8, 128, 300, True, 64), (32, 64, 8, 128, 200, True, 0),
                                                         (16, 16, 16, 128, 97, False, 0)])
 @pytest.mark.parametrize("poison", [False, True])
@@ -1270,6 +1274,77 @@ def test_decode_step_fused_fp8kv(B, Hq, Hkv, Smax, window):
         assert torch.isfinite(out).all()
         _close(out, o_ref)
     assert int(ws.tickets.abs().sum()) == 0
+
+
+def _decode_edge_case(B, Hq, Hkv, D, Smax, lens, kv_start=0, window=0, fp8=False, PS=None, tune=None):
+    """Two successive fused decode steps at chosen lengths (row b: lens[b % len(lens)], then one more)
+    against the references of test_decode_step_fused / test_decode_step_fused_fp8kv."""
+    g = torch.Generator().manual_seed(Smax + D + Hq)
+    W = (Hq + 2 * Hkv) * D
+    cos, sin = ref.rope_tables(D, 4096, 10000.0, DEV)
+    ks = vs = None
+    if fp8:
+        prompt = torch.randn(B * Smax, W, generator=g).to(torch.bfloat16).to(DEV)
+        kc = torch.zeros(B, Hkv, Smax, D, device=DEV, dtype=torch.uint8)
+        vc = torch.zeros_like(kc)
+        ks = torch.zeros(B, Hkv, (Smax + 15) // 16 * 16, device=DEV)
+        vs = torch.zeros_like(ks)
+        ops.kv_store_fp8(prompt, kc, vc, ks, vs, B, Smax, Hq)
+    else:
+        kc = torch.randn(B, Hkv, Smax, D, generator=g).to(torch.bfloat16).to(DEV)
+        vc = torch.randn(B, Hkv, Smax, D, generator=g).to(torch.bfloat16).to(DEV)
+    ws = ops.decode_workspace(B, Hq, Hkv, D, Smax, DEV, PS=PS)
+    bi = torch.arange(B, device=DEV)
+    for step in range(2):
+        attn_len = torch.tensor([lens[b % len(lens)] + step for b in range(B)], dtype=torch.int32, device=DEV)
+        slot = attn_len - 1
+        kvs = torch.clamp(slot, max=kv_start).to(torch.int32)
+        pos = (slot - kvs).to(torch.int32)
+        qkv = torch.randn(B, W, generator=g).to(torch.bfloat16).to(DEV)
+        kc2, vc2 = kc.clone(), vc.clone()
+        with ops.tuning(**tune) if tune else contextlib.nullcontext():
+            out = ops.decode_step_attention(qkv, kc, vc, slot, attn_len, Hq, pos, cos, sin, kvs, window, workspace=ws,
+                                            k_scale=ks, v_scale=vs)
+        assert torch.isfinite(out).all()
+        if fp8:
+            q = ops.rope_qkv_(qkv.clone(), pos, cos, sin, Hq, Hkv, D, S=1)
+            kq, ksn = ops.kv_quantize_rows(q[:, Hq * D:(Hq + Hkv) * D].reshape(B, Hkv, D), True)
+            vq, vsn = ops.kv_quantize_rows(q[:, (Hq + Hkv) * D:].reshape(B, Hkv, D), False)
+            torch.testing.assert_close(ks[bi, :, slot.long()], ksn, rtol=1e-6, atol=0)
+            torch.testing.assert_close(vs[bi, :, slot.long()], vsn, rtol=1e-6, atol=0)
+            assert (kc[bi, :, slot.long()].int() - kq.int()).abs().max().item() <= 1
+            assert (vc[bi, :, slot.long()].int() - vq.int()).abs().max().item() <= 1
+            kd = ops.kv_dequantize(kc, ks[..., :Smax], True)
+            vd = ops.kv_dequantize(vc, vs[..., :Smax], False)
+            o_ref = ref.decode_attention(q.float(), kd, vd, attn_len, Hq, kvs, window, 1.0 / math.sqrt(D))
+        else:
+            q_ref = ops.rope_qkv_(qkv.clone(), pos, cos, sin, Hq, Hkv, D, S=1, k_cache=kc2, v_cache=vc2, slot_base=slot)
+            o_ref = ref.decode_attention(q_ref, kc2, vc2, attn_len, Hq, kvs, window, 1.0 / math.sqrt(D))
+            assert torch.equal(kc, kc2) and torch.equal(vc, vc2), "cache append differs"
+        _close(out, o_ref)
+    assert int(ws.tickets.abs().sum()) == 0
+
+
+def test_decode_step_one_wave_mfma_g16_edges():
+    """16 query heads per kv head on the one-wave MFMA form (B * Hkv = 320), rows of 1 .. 47 keys"""
+    _decode_edge_case(160, 32, 2, 128, 48, [1, 15, 16, 17, 32, 33, 47])
+
+
+@pytest.mark.parametrize("attn_len,kv_start,window", [(1, 0, 0), (16, 0, 0), (17, 0, 0), (95, 0, 0),
+                                                      (95, 40, 0),  # the first two partitions are empty
+                                                      (95, 0, 8)])
+@pytest.mark.parametrize("fp8", [False, True])
+def test_decode_step_eight_wave_partition_edges(attn_len, kv_start, window, fp8):
+    """The 8-wave MFMA form over six 16-key partitions of a 96-slot cache: waves and partitions without
+    a tile, a full and a one-key last tile, empty leading partitions, a window inside one partition."""
+    _decode_edge_case(2, 8, 2, 128, 96, [attn_len], kv_start, window, fp8, PS=16,
+                      tune=dict(decode_mw_smax=32, decode_mw_kpp=16))
+
+
+def test_decode_step_valu_empty_leading_partition():
+    """The fused VALU kernel (head_dim 64) over three 128-key partitions with kv_start past the first:
+    partition 0 publishes an empty record, partition 2 holds no key of the 200-key rows either."""
+    _decode_edge_case(3, 8, 2, 64, 300, [200, 131, 258], kv_start=130, PS=128)
 
 
 def test_generation_fp8kv_matches_teacher_forcing():

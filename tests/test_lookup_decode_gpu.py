@@ -109,6 +109,13 @@ def test_verify_kernel_long_cache(D, Hq, Hkv, G):
     _verify_case(1, Hq, Hkv, D, G, 4096, 3000, 1024, cos, sin, seed=2)
 
 
+@pytest.mark.parametrize("D,Hq,Hkv,G,len0", [(128, 16, 2, 8, 1), (128, 16, 2, 8, 17),  # 64 rows: four row tiles
+                                             (64, 8, 2, 4, 257)])  # two partitions; row 1 ends inside the first
+def test_verify_kernel_row_tile_and_partition_edges(D, Hq, Hkv, G, len0):
+    cos, sin = ref.rope_tables(D, 512)
+    _verify_case(2, Hq, Hkv, D, G, 96 if D == 128 else 512, len0, 0, cos, sin, seed=len0, successive=True)
+
+
 def test_drafter_kernel_matches_twin():
     for (rows, K, ngram, inp, nd, ra), (_, _, _, inp_c, nd_c, ra_c) in zip(cpu_cases.run_draft(cpu_cases.DRAFT_CASES, DEV),
                                                                          cpu_cases.run_draft(cpu_cases.DRAFT_CASES)):
