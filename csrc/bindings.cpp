@@ -71,6 +71,8 @@ int rt_logprob_bwd(const void*, int, long, const long*, float, long, int, const 
                    const float*, void*, long, hipStream_t);
 int rt_sample(const void*, int, long, long, int, float, int, float, int, uint64_t, const int64_t*, const uint8_t*, long*,
               float*, hipStream_t);
+int rt_sample_rows(const void*, int, long, long, int, const float*, const int*, const float*, const uint8_t*,
+                   const int64_t*, const int*, const uint8_t*, long*, float*, hipStream_t);
 int rt_grad_sumsq(const float*, long, float*, int, hipStream_t);
 int rt_adamw(float*, const float*, float*, float*, void*, long, float, float, float, float, float, int, float,
              const float*, int, float*, int*, hipStream_t);
@@ -94,6 +96,9 @@ int rt_ppo_loss(const float*, const float*, const float*, const float*, const fl
 int rt_rowdot(const void*, long, const float*, const float*, int, long, float*, hipStream_t);
 int rt_decode_update(const long*, long*, int, float*, const float*, float*, const float*, uint8_t*, int*, int*, long*,
                      int*, int64_t*, int64_t*, int, const long*, int, long, int*, const int*, hipStream_t);
+int rt_decode_update_rows(const long*, long*, int, float*, const float*, float*, const float*, uint8_t*, int*, int*,
+                          long*, int*, int64_t*, int64_t*, int, const long*, int, long, int*, const int*, const int*,
+                          hipStream_t);
 int rt_attn_verify(const void*, long, void*, void*, int, const int*, const int*, const int*, const int*, const float*,
                    const float*, float, int, void*, long, int, int, int, int, int, float, int, hipStream_t);
 int rt_lookup_accept(const long*, const float*, const long*, const int*, int, long*, float*, int, long*, int, uint8_t*,
@@ -1174,6 +1179,36 @@ void sample(const Tensor& logits, double inv_temp, int64_t top_k, double top_p, 
            "sample");
 }
 
+// Per-row sampling parameters, all [B] device tensors read by the kernels (a captured graph sees
+// new values on replay); the Philox stream of row b is keyed by (seed[b], counter[b]) alone.
+void sample_rows(const Tensor& logits, const Tensor& inv_temp, const Tensor& top_k, const Tensor& top_p,
+                 const Tensor& greedy, const Tensor& seed, const Tensor& counter, const optional<Tensor>& active,
+                 Tensor out_tok, const optional<Tensor>& out_logp) {
+  CHECK_CUDA(logits); CHECK_ROWS(logits); CHECK_I64(out_tok);
+  TORCH_CHECK(logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16,
+              "sample_rows: logits must be float32 or bfloat16");
+  const bool f32 = logits.scalar_type() == at::kFloat;
+  const int64_t B = logits.size(0);
+  CHECK_F32(inv_temp); CHECK_I32(top_k); CHECK_F32(top_p); CHECK_I64(seed); CHECK_I32(counter);
+  TORCH_CHECK(greedy.scalar_type() == at::kByte || greedy.scalar_type() == at::kBool, "greedy must be uint8 or bool");
+  auto row_vec = [&](const Tensor& t, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.get_device() == logits.get_device(), "sample_rows: ", name, " must be on the logits' device");
+    TORCH_CHECK(t.dim() == 1 && t.is_contiguous() && t.numel() == B, "sample_rows: ", name, " must be contiguous [B]");
+  };
+  row_vec(inv_temp, "inv_temp"); row_vec(top_k, "top_k"); row_vec(top_p, "top_p"); row_vec(greedy, "greedy");
+  row_vec(seed, "seed"); row_vec(counter, "counter"); row_vec(out_tok, "out_tok");
+  if (active.has_value() && active->defined()) {
+    TORCH_CHECK(active->scalar_type() == at::kByte || active->scalar_type() == at::kBool, "active must be uint8 or bool");
+    row_vec(*active, "active");
+  }
+  if (out_logp.has_value() && out_logp->defined()) { CHECK_F32(*out_logp); row_vec(*out_logp, "out_logp"); }
+  check_rc(rt_sample_rows(logits.data_ptr(), f32, logits.stride(0), B, (int)logits.size(1), inv_temp.data_ptr<float>(),
+                          top_k.data_ptr<int>(), top_p.data_ptr<float>(), (const uint8_t*)greedy.data_ptr(),
+                          (const int64_t*)seed.data_ptr(), counter.data_ptr<int>(), (const uint8_t*)opt_ptr(active),
+                          (long*)out_tok.data_ptr(), (float*)opt_ptr(out_logp), cur_stream()),
+           "sample_rows");
+}
+
 // ---------------------------------------------------------------------------------------------
 void adamw(Tensor p, const Tensor& g, Tensor m, Tensor v, const optional<Tensor>& pbf, double lr, double b1, double b2,
            double eps, double wd, int64_t step, double max_norm, Tensor partials, Tensor norm_out, Tensor skipped) {
@@ -1431,6 +1466,34 @@ void decode_update(const Tensor& tok, Tensor out_tokens, const optional<Tensor>&
            "decode_update");
 }
 
+// decode_update with a per-row answer length: row b finishes at min(row_max_new[b], output width)
+void decode_update_rows(const Tensor& tok, Tensor out_tokens, const optional<Tensor>& out_logp,
+                        const optional<Tensor>& logp, const optional<Tensor>& out_values,
+                        const optional<Tensor>& values, Tensor active, Tensor kv_len, Tensor pos, Tensor next_input,
+                        Tensor gen_len, Tensor step, Tensor rng_offset, const Tensor& eos_ids, int64_t pad_id,
+                        const optional<Tensor>& attn_len, const optional<Tensor>& kv_start, const Tensor& row_max_new) {
+  CHECK_I64(tok); CHECK_I64(out_tokens); CHECK_I32(kv_len); CHECK_I32(pos); CHECK_I64(next_input); CHECK_I32(gen_len);
+  const bool al = attn_len.has_value() && attn_len->defined();
+  if (al) {
+    CHECK_I32(*attn_len);
+    TORCH_CHECK(attn_len->numel() >= tok.numel(), "decode_update_rows: attn_len");
+  }
+  if (kv_start.has_value() && kv_start->defined()) CHECK_I32(*kv_start);
+  CHECK_I64(step); CHECK_I64(rng_offset); CHECK_I64(eos_ids);
+  TORCH_CHECK(active.scalar_type() == at::kByte || active.scalar_type() == at::kBool);
+  CHECK_CUDA(row_max_new); CHECK_I32(row_max_new);
+  TORCH_CHECK(row_max_new.is_contiguous() && row_max_new.numel() == tok.numel(), "decode_update_rows: row_max_new [B]");
+  check_rc(rt_decode_update_rows((const long*)tok.data_ptr(), (long*)out_tokens.data_ptr(), (int)out_tokens.size(1),
+                                 (float*)opt_ptr(out_logp), (const float*)opt_ptr(logp), (float*)opt_ptr(out_values),
+                                 (const float*)opt_ptr(values), (uint8_t*)active.data_ptr(), kv_len.data_ptr<int>(),
+                                 pos.data_ptr<int>(), (long*)next_input.data_ptr(), gen_len.data_ptr<int>(),
+                                 (int64_t*)step.data_ptr(), (int64_t*)rng_offset.data_ptr(), (int)tok.numel(),
+                                 (const long*)eos_ids.data_ptr(), (int)eos_ids.numel(), (long)pad_id,
+                                 al ? attn_len->data_ptr<int>() : nullptr, (const int*)opt_ptr(kv_start),
+                                 row_max_new.data_ptr<int>(), cur_stream()),
+           "decode_update_rows");
+}
+
 // Verify step of prompt-lookup decoding: rows b * G + j of qkv are G consecutive positions of
 // sequence b (RoPE at pos0 + j, K / V appended at slot0 + j, keys < attn_len0 + j visible).
 void attn_verify(const Tensor& qkv, Tensor kc, Tensor vc, const Tensor& slot0, const Tensor& attn_len0,
@@ -1575,6 +1638,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("logprob_fwd", &logprob_fwd);
   m.def("logprob_bwd", &logprob_bwd);
   m.def("sample", &sample);
+  m.def("sample_rows", &sample_rows);
   m.def("adamw", &adamw);
   m.def("scatter_scaled", &scatter_scaled, "batched scaled fp32 -> bf16 strided scatter (LoRA images)");
   m.def("lora_grad_accum", &lora_grad_accum, "LoRA backward: scaled sum of adapter-gradient slabs into grads");
@@ -1591,6 +1655,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ppo_loss", &ppo_loss, "fused token-level PPO loss: {stats[9], dlp, dv, dent}");
   m.def("rowdot", &rowdot, "value head: batch-invariant per-row dot product");
   m.def("decode_update", &decode_update);
+  m.def("decode_update_rows", &decode_update_rows);
   m.def("attn_verify", &attn_verify, "verify step: RoPE + KV append + attention of G consecutive positions per row");
   m.def("lookup_accept", &lookup_accept, "prompt-lookup decoding: accept / emit bookkeeping of a verify step");
   m.def("lookup_draft", &lookup_draft, "prompt-lookup decoding: next inputs = last token + n-gram draft");

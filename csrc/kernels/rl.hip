@@ -95,7 +95,8 @@ __global__ __launch_bounds__(256) void ppo_advantages_kernel(const float* __rest
 
 // After sampling token `tok[b]` at decode step `step`: record it, update finished flags (eos or
 // length budget), advance per-row cache length/position, bump the RNG offset and step counter.
-// Rows that are finished keep emitting pad and stop advancing.
+// Rows that are finished keep emitting pad and stop advancing. `row_max_new` (optional, [B]): the
+// row's own answer length; a row finishes at min(row_max_new[b], max_new).
 __global__ void decode_update_kernel(const long* __restrict__ tok, long* __restrict__ out_tokens, int max_new,
                                      float* __restrict__ out_logp, const float* __restrict__ logp,
                                      float* __restrict__ out_values, const float* __restrict__ values,
@@ -103,7 +104,8 @@ __global__ void decode_update_kernel(const long* __restrict__ tok, long* __restr
                                      long* __restrict__ next_input, int* __restrict__ gen_len,
                                      int64_t* __restrict__ step, int64_t* __restrict__ rng_offset, int B,
                                      const long* __restrict__ eos_ids, int n_eos, long pad_id,
-                                     int* __restrict__ attn_len, const int* __restrict__ kv_start) {
+                                     int* __restrict__ attn_len, const int* __restrict__ kv_start,
+                                     const int* __restrict__ row_max_new) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t s = *step;
   if (b < B) {
@@ -118,7 +120,7 @@ __global__ void decode_update_kernel(const long* __restrict__ tok, long* __restr
       if (out_logp) out_logp[(long)b * max_new + sr] = logp[b];
       if (out_values && values) out_values[(long)b * max_new + sr] = values[b];
       gen_len[b] = sr + 1;
-      bool fin = (sr + 1 >= max_new);
+      bool fin = (sr + 1 >= (row_max_new ? min(row_max_new[b], max_new) : max_new));
       for (int e = 0; e < n_eos; ++e) fin = fin || (t == eos_ids[e]);
       if (fin) active[b] = 0;
       kv_len[b] += 1;
@@ -429,7 +431,21 @@ extern "C" int rt_decode_update(const long* tok, long* out_tokens, int max_new, 
   if (B > 1024) return -1;
   hipLaunchKernelGGL(decode_update_kernel, dim3(1), dim3(((B + 63) / 64) * 64), 0, stream, tok, out_tokens, max_new,
                      out_logp, logp, out_values, values, active, kv_len, pos, next_input, gen_len, step, rng_offset, B,
-                     eos_ids, n_eos, pad_id, attn_len, kv_start);
+                     eos_ids, n_eos, pad_id, attn_len, kv_start, (const int*)nullptr);
+  RT_LAUNCH_CHECK();
+  return 0;
+}
+
+// The same bookkeeping with a per-row answer length (continuous batching with per-request sampling).
+extern "C" int rt_decode_update_rows(const long* tok, long* out_tokens, int max_new, float* out_logp,
+                                     const float* logp, float* out_values, const float* values, uint8_t* active,
+                                     int* kv_len, int* pos, long* next_input, int* gen_len, int64_t* step,
+                                     int64_t* rng_offset, int B, const long* eos_ids, int n_eos, long pad_id,
+                                     int* attn_len, const int* kv_start, const int* row_max_new, hipStream_t stream) {
+  if (B > 1024 || !row_max_new) return -1;
+  hipLaunchKernelGGL(decode_update_kernel, dim3(1), dim3(((B + 63) / 64) * 64), 0, stream, tok, out_tokens, max_new,
+                     out_logp, logp, out_values, values, active, kv_len, pos, next_input, gen_len, step, rng_offset, B,
+                     eos_ids, n_eos, pad_id, attn_len, kv_start, row_max_new);
   RT_LAUNCH_CHECK();
   return 0;
 }

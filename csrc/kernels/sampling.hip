@@ -24,12 +24,16 @@ template <typename T> __device__ __forceinline__ float ld1(const T* p);
 template <> __device__ __forceinline__ float ld1<bf16_t>(const bf16_t* p) { return bf2f(*p); }
 template <> __device__ __forceinline__ float ld1<float>(const float* p) { return *p; }
 
-template <typename T>
-__global__ __launch_bounds__(256) void sample_kernel(const T* __restrict__ logits, long ld, int V, float inv_temp,
-                                                     int top_k, float top_p, int greedy, uint64_t seed,
-                                                     const int64_t* __restrict__ offset_ptr,
-                                                     const uint8_t* __restrict__ row_active, long* __restrict__ out_tok,
-                                                     float* __restrict__ out_logp) {
+// Each sampler below is a row body (one workgroup samples the row `x`) shared by two launch forms:
+// the scalar kernels pass one set of launch scalars for every row, the Philox subsequence `subseq`
+// = the row index and `offp()` = *offset_ptr; the per-row kernels (sample_rows_*, end of the file)
+// read the row's parameters from device memory, with subsequence 0 and offp() = counter[row].
+// `offp` is only called by a row that draws.
+template <typename T, typename OffFn>
+__device__ __forceinline__ void sample_row_radix(const T* __restrict__ x, long row, uint64_t subseq, int V,
+                                                 float inv_temp, int top_k, float top_p, int greedy, uint64_t seed,
+                                                 OffFn offp, const uint8_t* __restrict__ row_active,
+                                                 long* __restrict__ out_tok, float* __restrict__ out_logp) {
   __shared__ float hist_f[256];
   __shared__ unsigned hist_c[256];
   __shared__ float redf[8];
@@ -37,8 +41,6 @@ __global__ __launch_bounds__(256) void sample_kernel(const T* __restrict__ logit
   __shared__ uint32_t sh_key;
   __shared__ float sh_f;
 
-  const long row = blockIdx.x;
-  const T* x = logits + row * ld;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
 
   // pass 1: max of tempered logits (and argmax for greedy)
@@ -140,13 +142,13 @@ __global__ __launch_bounds__(256) void sample_kernel(const T* __restrict__ logit
       pth = prefix > kth ? prefix : kth;
     }
     // ---- Gumbel-max draw over kept tokens ----
-    const uint64_t off = offset_ptr ? (uint64_t)offset_ptr[0] : 0ull;
+    const uint64_t off = offp();
     float best = -INFINITY;
     int bi = AM;
     for (int i = tid; i < V; i += 256) {
       const float f = ld1<T>(x + i);
       if (fkey(f) >= pth) {
-        const uint4 r = Philox::gen(seed, (uint64_t)row, off * (uint64_t)V + (uint64_t)i);
+        const uint4 r = Philox::gen(seed, subseq, off * (uint64_t)V + (uint64_t)i);
         const float u = u32_to_unit(r.x);
         const float gmb = -__logf(-__logf(u));
         const float sc = f * inv_temp + gmb;
@@ -178,6 +180,17 @@ __global__ __launch_bounds__(256) void sample_kernel(const T* __restrict__ logit
   }
 }
 
+template <typename T>
+__global__ __launch_bounds__(256) void sample_kernel(const T* __restrict__ logits, long ld, int V, float inv_temp,
+                                                     int top_k, float top_p, int greedy, uint64_t seed,
+                                                     const int64_t* __restrict__ offset_ptr,
+                                                     const uint8_t* __restrict__ row_active, long* __restrict__ out_tok,
+                                                     float* __restrict__ out_logp) {
+  const long row = blockIdx.x;
+  sample_row_radix<T>(logits + row * ld, row, (uint64_t)row, V, inv_temp, top_k, top_p, greedy, seed,
+                      [=]() -> uint64_t { return offset_ptr ? (uint64_t)offset_ptr[0] : 0ull; }, row_active, out_tok,
+                      out_logp);
+}
 
 // ---------------------------------------------------------------------------------------------
 // bf16 fast path: the row (<= 80k tokens) is staged ONCE in LDS as 16-bit order-preserving keys;
@@ -192,19 +205,17 @@ __device__ __forceinline__ float key16_to_f(uint32_t k) {
   return bf2f(b);
 }
 
-__global__ __launch_bounds__(256) void sample_bf16_lds_kernel(const bf16_t* __restrict__ logits, long ld, int V,
-                                                              float inv_temp, int top_k, float top_p, int greedy,
-                                                              uint64_t seed, const int64_t* __restrict__ offset_ptr,
-                                                              const uint8_t* __restrict__ row_active,
-                                                              long* __restrict__ out_tok, float* __restrict__ out_logp) {
+template <typename OffFn>
+__device__ __forceinline__ void sample_row_bf16_lds(const bf16_t* __restrict__ x, long row, uint64_t subseq, int V,
+                                                    float inv_temp, int top_k, float top_p, int greedy, uint64_t seed,
+                                                    OffFn offp, const uint8_t* __restrict__ row_active,
+                                                    long* __restrict__ out_tok, float* __restrict__ out_logp) {
   extern __shared__ __attribute__((aligned(16))) uint16_t keys[];   // [V] (+ pad) 16-bit keys
   __shared__ float hist[4][256];
   __shared__ float redf[8];
   __shared__ int redi[8];
   __shared__ uint32_t sh_sel;
   __shared__ float sh_f;
-  const long row = blockIdx.x;
-  const bf16_t* x = logits + row * ld;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int nv = V / 8;
 
@@ -320,13 +331,13 @@ __global__ __launch_bounds__(256) void sample_bf16_lds_kernel(const bf16_t* __re
       }
       pth = prefix > kth ? prefix : kth;
     }
-    const uint64_t off = offset_ptr ? (uint64_t)offset_ptr[0] : 0ull;
+    const uint64_t off = offp();
     float best = -INFINITY;
     int bi = AM;
     for (int i = tid; i < V; i += 256) {
       const uint32_t k = keys[i];
       if (k >= pth) {
-        const uint4 r = Philox::gen(seed, (uint64_t)row, off * (uint64_t)V + (uint64_t)i);
+        const uint4 r = Philox::gen(seed, subseq, off * (uint64_t)V + (uint64_t)i);
         const float gmb = -__logf(-__logf(u32_to_unit(r.x)));
         const float sc = key16_to_f(k) * inv_temp + gmb;
         if (sc > best || (sc == best && i < bi)) { best = sc; bi = i; }
@@ -355,6 +366,17 @@ __global__ __launch_bounds__(256) void sample_bf16_lds_kernel(const bf16_t* __re
     out_tok[row] = tok;
     if (out_logp) out_logp[row] = key16_to_f(keys[tok]) * inv_temp - lse;
   }
+}
+
+__global__ __launch_bounds__(256) void sample_bf16_lds_kernel(const bf16_t* __restrict__ logits, long ld, int V,
+                                                              float inv_temp, int top_k, float top_p, int greedy,
+                                                              uint64_t seed, const int64_t* __restrict__ offset_ptr,
+                                                              const uint8_t* __restrict__ row_active,
+                                                              long* __restrict__ out_tok, float* __restrict__ out_logp) {
+  const long row = blockIdx.x;
+  sample_row_bf16_lds(logits + row * ld, row, (uint64_t)row, V, inv_temp, top_k, top_p, greedy, seed,
+                      [=]() -> uint64_t { return offset_ptr ? (uint64_t)offset_ptr[0] : 0ull; }, row_active, out_tok,
+                      out_logp);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -447,10 +469,11 @@ __device__ __forceinline__ int block_sum_int1024(int v, int* red) {
   return t;
 }
 
-__global__ __launch_bounds__(1024) void sample_topk_search_kernel(
-    const bf16_t* __restrict__ logits, long ld, int V, float inv_temp, int top_k, float top_p, uint64_t seed,
-    const int64_t* __restrict__ offset_ptr, const uint8_t* __restrict__ row_active, long* __restrict__ out_tok,
-    float* __restrict__ out_logp, int flags) {
+template <typename OffFn>
+__device__ __forceinline__ void sample_row_search(const bf16_t* __restrict__ x, long row, uint64_t subseq, int V,
+                                                  float inv_temp, int top_k, float top_p, uint64_t seed, OffFn offp,
+                                                  const uint8_t* __restrict__ row_active, long* __restrict__ out_tok,
+                                                  float* __restrict__ out_logp, int flags) {
   // flags bit 0: candidate window (tuning sample_window); bit 1: the <= 64-survivor wave-0 fast
   // path (tuning sample_fast64; 0 sends those rows through the block-wide sort / top-p / Gumbel
   // path, the same arithmetic — tests pin the two bitwise)
@@ -462,8 +485,6 @@ __global__ __launch_bounds__(1024) void sample_topk_search_kernel(
   __shared__ int redi[16][NWIN / 2 + 1];
   __shared__ float redf[16];
   __shared__ int cnt;
-  const long row = blockIdx.x;
-  const bf16_t* x = logits + row * ld;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int nv = V / 8;
 
@@ -724,11 +745,11 @@ __global__ __launch_bounds__(1024) void sample_topk_search_kernel(
         const int src = m ? __ffsll((long long)m) - 1 : n - 1;
         vthr = __shfl(v, src, 64);
       }
-      const uint64_t off = offset_ptr ? (uint64_t)offset_ptr[0] : 0ull;
+      const uint64_t off = offp();
       float best = -INFINITY;
       int bi = AM;
       if (lane < n && v >= vthr) {
-        const uint4 r = Philox::gen(seed, (uint64_t)row, off * (uint64_t)V + (uint64_t)ix);
+        const uint4 r = Philox::gen(seed, subseq, off * (uint64_t)V + (uint64_t)ix);
         best = v - __logf(-__logf(u32_to_unit(r.x)));
         bi = ix;
       }
@@ -818,7 +839,7 @@ __global__ __launch_bounds__(1024) void sample_topk_search_kernel(
       __syncthreads();
     }
     // Gumbel-max over the kept survivors
-    const uint64_t off = offset_ptr ? (uint64_t)offset_ptr[0] : 0ull;
+    const uint64_t off = offp();
     float best = -INFINITY;
     int bi = AM;
     if (!overflow) {
@@ -826,7 +847,7 @@ __global__ __launch_bounds__(1024) void sample_topk_search_kernel(
         const float v = lval[j];
         if (v >= vthr) {
           const int i = lidx[j];
-          const uint4 r = Philox::gen(seed, (uint64_t)row, off * (uint64_t)V + (uint64_t)i);
+          const uint4 r = Philox::gen(seed, subseq, off * (uint64_t)V + (uint64_t)i);
           const float sc = v - __logf(-__logf(u32_to_unit(r.x)));
           if (sc > best || (sc == best && i < bi)) { best = sc; bi = i; }
         }
@@ -835,7 +856,7 @@ __global__ __launch_bounds__(1024) void sample_topk_search_kernel(
       for (int i = tid; i < V; i += 1024) {
         const uint32_t k = keys[i];
         if (k >= kth) {
-          const uint4 r = Philox::gen(seed, (uint64_t)row, off * (uint64_t)V + (uint64_t)i);
+          const uint4 r = Philox::gen(seed, subseq, off * (uint64_t)V + (uint64_t)i);
           const float sc = key16_to_f(k) * inv_temp - __logf(-__logf(u32_to_unit(r.x)));
           if (sc > best || (sc == best && i < bi)) { best = sc; bi = i; }
         }
@@ -864,6 +885,72 @@ __global__ __launch_bounds__(1024) void sample_topk_search_kernel(
     out_tok[row] = tok;
     if (out_logp) out_logp[row] = key16_to_f(keys[tok]) * inv_temp - lse;
   }
+}
+
+__global__ __launch_bounds__(1024) void sample_topk_search_kernel(
+    const bf16_t* __restrict__ logits, long ld, int V, float inv_temp, int top_k, float top_p, uint64_t seed,
+    const int64_t* __restrict__ offset_ptr, const uint8_t* __restrict__ row_active, long* __restrict__ out_tok,
+    float* __restrict__ out_logp, int flags) {
+  const long row = blockIdx.x;
+  sample_row_search(logits + row * ld, row, (uint64_t)row, V, inv_temp, top_k, top_p, seed,
+                    [=]() -> uint64_t { return offset_ptr ? (uint64_t)offset_ptr[0] : 0ull; }, row_active, out_tok,
+                    out_logp, flags);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Per-row parameters (continuous batching with per-request sampling): every row reads its own
+// inverse temperature, top-k, top-p, greedy flag, seed and counter from device memory, so one
+// captured decode step serves any mix of settings. The Philox stream of row b is
+// (seed[b], subsequence 0, counter[b] * V + token): what a one-row launch of the scalar kernels
+// draws with seed = seed[b] and *offset_ptr = counter[b], whatever row the request sits in and
+// whoever shares the batch. A row's parameters are uniform across its workgroup, so which body a
+// row runs is a workgroup-uniform branch: rows with 1 <= top_k <= 1024 that draw take the
+// 1024-thread search body (sample_rows_search_kernel, when the logits qualify for it), every other
+// row the 256-thread radix body; each kernel's workgroups of the other kind exit at once.
+// ---------------------------------------------------------------------------------------------
+struct RowParams {
+  const float* inv_temp;
+  const int* top_k;
+  const float* top_p;
+  const uint8_t* greedy;
+  const int64_t* seed;
+  const int* counter;
+};
+__device__ __forceinline__ bool row_takes_search(const RowParams& p, long row) {
+  const int k = p.top_k[row];
+  return !p.greedy[row] && k >= 1 && k <= 1024;
+}
+
+__global__ __launch_bounds__(1024) void sample_rows_search_kernel(const bf16_t* __restrict__ logits, long ld, int V,
+                                                                  RowParams p, const uint8_t* __restrict__ row_active,
+                                                                  long* __restrict__ out_tok,
+                                                                  float* __restrict__ out_logp, int flags) {
+  const long row = blockIdx.x;
+  if (!row_takes_search(p, row)) return;
+  const int* counter = p.counter;
+  sample_row_search(logits + row * ld, row, 0ull, V, p.inv_temp[row], p.top_k[row], p.top_p[row],
+                    (uint64_t)p.seed[row], [=]() -> uint64_t { return (uint64_t)counter[row]; }, row_active, out_tok,
+                    out_logp, flags);
+}
+
+// LDS = true: bf16 rows staged as 16-bit keys (sample_row_bf16_lds); search_rows: the launch is
+// paired with sample_rows_search_kernel, whose rows are skipped here
+template <typename T, bool LDS>
+__global__ __launch_bounds__(256) void sample_rows_radix_kernel(const T* __restrict__ logits, long ld, int V,
+                                                                RowParams p, int search_rows,
+                                                                const uint8_t* __restrict__ row_active,
+                                                                long* __restrict__ out_tok,
+                                                                float* __restrict__ out_logp) {
+  const long row = blockIdx.x;
+  if (search_rows && row_takes_search(p, row)) return;
+  const int* counter = p.counter;
+  auto offp = [=]() -> uint64_t { return (uint64_t)counter[row]; };
+  if constexpr (LDS)
+    sample_row_bf16_lds(logits + row * ld, row, 0ull, V, p.inv_temp[row], p.top_k[row], p.top_p[row],
+                        (int)p.greedy[row], (uint64_t)p.seed[row], offp, row_active, out_tok, out_logp);
+  else
+    sample_row_radix<T>(logits + row * ld, row, 0ull, V, p.inv_temp[row], p.top_k[row], p.top_p[row],
+                        (int)p.greedy[row], (uint64_t)p.seed[row], offp, row_active, out_tok, out_logp);
 }
 
 }  // namespace rt
@@ -895,6 +982,32 @@ extern "C" int rt_sample(const void* logits, int is_f32, long ld, long B, int V,
   else
     hipLaunchKernelGGL(sample_kernel<bf16_t>, dim3(B), dim3(256), 0, stream, (const bf16_t*)logits, ld, V, inv_temp,
                        top_k, top_p, greedy, seed, offset_ptr, row_active, out_tok, out_logp);
+  RT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int rt_sample_rows(const void* logits, int is_f32, long ld, long B, int V, const float* inv_temp,
+                              const int* top_k, const float* top_p, const uint8_t* greedy, const int64_t* seed,
+                              const int* counter, const uint8_t* row_active, long* out_tok, float* out_logp,
+                              hipStream_t stream) {
+  if (B == 0) return 0;
+  const RowParams p{inv_temp, top_k, top_p, greedy, seed, counter};
+  const bool lds = !is_f32 && V % 8 == 0 && ld % 8 == 0 && (size_t)V * 2 <= 96 * 1024;
+  if (lds) {
+    const size_t shm = ((size_t)V * 2 + 15) / 16 * 16;
+    hipLaunchKernelGGL(sample_rows_search_kernel, dim3(B), dim3(1024), shm, stream, (const bf16_t*)logits, ld, V, p,
+                       row_active, out_tok, out_logp,
+                       (tuning().sample_window ? 1 : 0) | (tuning().sample_fast64 ? 2 : 0));
+    RT_LAUNCH_CHECK();
+    hipLaunchKernelGGL((sample_rows_radix_kernel<bf16_t, true>), dim3(B), dim3(256), shm, stream,
+                       (const bf16_t*)logits, ld, V, p, 1, row_active, out_tok, out_logp);
+  } else if (is_f32) {
+    hipLaunchKernelGGL((sample_rows_radix_kernel<float, false>), dim3(B), dim3(256), 0, stream, (const float*)logits,
+                       ld, V, p, 0, row_active, out_tok, out_logp);
+  } else {
+    hipLaunchKernelGGL((sample_rows_radix_kernel<bf16_t, false>), dim3(B), dim3(256), 0, stream,
+                       (const bf16_t*)logits, ld, V, p, 0, row_active, out_tok, out_logp);
+  }
   RT_LAUNCH_CHECK();
   return 0;
 }

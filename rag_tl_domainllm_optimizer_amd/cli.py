@@ -410,7 +410,9 @@ def cmd_pipeline(cfg, args):
 def cmd_serve(cfg, args):
     from .serve import serve
 
-    serve(cfg, host=args.host, port=args.port)
+    if args.per_request_sampling is not None:
+        cfg.serve.per_request_sampling = args.per_request_sampling
+    serve(cfg, host=args.host, port=args.port, per_request_sampling=cfg.serve.per_request_sampling)
 
 
 def cmd_bench(cfg, args, rest):
@@ -443,6 +445,8 @@ def main(argv: Optional[List[str]] = None):
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=8000)
     ap.add_argument("--nproc", type=int, default=1)
+    ap.add_argument("--per-request-sampling", dest="per_request_sampling", action=argparse.BooleanOptionalAction,
+                    default=None, help="serve: accept per-request sampling settings (serve.per_request_sampling)")
     ap.add_argument("--env", action="append", default=[], help="launch: KEY=VALUE set for every rank (repeatable)")
     ap.add_argument("--resume", action="store_true",
                     help="sft / ppo / pipeline: continue from the run's latest checkpoint")

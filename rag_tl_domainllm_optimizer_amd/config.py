@@ -65,6 +65,13 @@ class RetrievalSection:
 
 
 @dataclass
+class ServeSection:
+    # requests may carry their own temperature / top-k / top-p / greedy flag / seed / answer length
+    # (continuous batching; the sampled stream then differs from the one-configuration server's)
+    per_request_sampling: bool = False
+
+
+@dataclass
 class RunConfig:
     name: str = "run"
     out_dir: str = "runs"
@@ -76,6 +83,7 @@ class RunConfig:
     sft: SFTConfig = field(default_factory=SFTConfig)
     raft: RaftConfig = field(default_factory=RaftConfig)
     eval: EvalConfig = field(default_factory=EvalConfig)
+    serve: ServeSection = field(default_factory=ServeSection)
     use_wandb: bool = False
 
 

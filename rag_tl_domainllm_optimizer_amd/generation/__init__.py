@@ -46,6 +46,75 @@ class SamplingParams:
         return 1.0 if self.greedy else 1.0 / self.temperature
 
 
+_MIX = 0x9E3779B97F4A7C15  # 2**64 / golden ratio: spreads consecutive integers over 64 bits
+
+
+def derive_seed(base_seed: int, count: int) -> int:
+    """The seed of the ``count``-th request that brought none of its own: a fixed function of the
+    batcher's ``SamplingParams.seed`` and the admission count (splitmix64's finaliser), < 2**63."""
+    z = (int(base_seed) * _MIX + (int(count) + 1) * 0xBF58476D1CE4E5B9) & (2 ** 64 - 1)
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & (2 ** 64 - 1)
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & (2 ** 64 - 1)
+    return (z ^ (z >> 31)) & (2 ** 63 - 1)
+
+
+@dataclass
+class RequestSampling:
+    """One request's sampling settings under ``ContinuousBatcher(per_request=True)``; a field left
+    ``None`` takes the batcher's ``SamplingParams`` value (an unseeded request: ``derive_seed``)."""
+    temperature: Optional[float] = None   # 0: greedy
+    top_k: Optional[int] = None           # 0: off
+    top_p: Optional[float] = None
+    do_sample: Optional[bool] = None
+    seed: Optional[int] = None
+    max_new_tokens: Optional[int] = None
+
+    def validate(self, max_new: Optional[int] = None):
+        """ValueError for a setting outside its range (``max_new``: the batcher's output width)."""
+        if self.temperature is not None and not self.temperature >= 0:
+            raise ValueError(f"temperature = {self.temperature}: must be >= 0 (0 = greedy)")
+        if self.top_k is not None and not self.top_k >= 0:
+            raise ValueError(f"top_k = {self.top_k}: must be >= 0 (0 = off)")
+        if self.top_p is not None and not 0 < self.top_p <= 1:
+            raise ValueError(f"top_p = {self.top_p}: must be in (0, 1]")
+        if self.max_new_tokens is not None and not (self.max_new_tokens >= 1 and
+                                                    (max_new is None or self.max_new_tokens <= max_new)):
+            raise ValueError(f"max_new_tokens = {self.max_new_tokens}: must be in [1, "
+                             f"{max_new if max_new is not None else 'the output width'}]")
+        if self.seed is not None and not 0 <= self.seed < 2 ** 63:
+            raise ValueError(f"seed = {self.seed}: must be in [0, 2**63)")
+
+    def resolve(self, params: SamplingParams, max_new: int, default_seed: int):
+        """(inv_temp, top_k, top_p, greedy, seed, max_new_tokens) with the batcher's defaults filled in"""
+        self.validate(max_new)
+        pick = lambda v, d: d if v is None else v  # noqa: E731
+        temp = float(pick(self.temperature, params.temperature))
+        greedy = (not pick(self.do_sample, params.do_sample)) or temp <= 0
+        return (1.0 if greedy else 1.0 / temp, int(pick(self.top_k, params.top_k)),
+                float(pick(self.top_p, params.top_p)), bool(greedy), int(pick(self.seed, default_seed)),
+                int(pick(self.max_new_tokens, max_new)))
+
+
+class _RowParams:
+    """Static per-row sampling parameters (device memory the captured decode step reads)."""
+
+    def __init__(self, B: int, device):
+        self.inv_temp = torch.ones(B, dtype=torch.float32, device=device)
+        self.top_k = torch.zeros(B, dtype=torch.int32, device=device)
+        self.top_p = torch.ones(B, dtype=torch.float32, device=device)
+        self.greedy = torch.zeros(B, dtype=torch.uint8, device=device)
+        self.seed = torch.zeros(B, dtype=torch.long, device=device)
+        self.max_new = torch.ones(B, dtype=torch.int32, device=device)
+
+    def tensors(self):
+        return [self.inv_temp, self.top_k, self.top_p, self.greedy, self.seed, self.max_new]
+
+    def write(self, b0: int, rows):
+        """rows: ``RequestSampling.resolve`` tuples of rows b0.. (host-to-device copies, outside any graph)"""
+        for t, col in zip(self.tensors(), zip(*rows)):
+            t[b0:b0 + len(rows)].copy_(torch.tensor(col, dtype=t.dtype))
+
+
 @dataclass
 class GenerationOutput:
     tokens: torch.Tensor        # [B, T] generated ids (pad after finish)
@@ -179,6 +248,10 @@ class Generator:
         self.hist = None
         self._lookup = {}
         self._lk = None
+        # per-request sampling (ContinuousBatcher(per_request=True)): per-row parameter buffers,
+        # allocated on first use; _rows_on selects the per-row sampler and bookkeeping in _emit
+        self.rowp = None
+        self._rows_on = False
 
     # ------------------------------------------------------------------ one decode step (device only)
     def _bucket(self, B: int) -> int:
@@ -206,6 +279,11 @@ class Generator:
         if st is None:
             st = self._lookup[K] = _LookupState(self.max_batch, K + 1, self.device)
         return st
+
+    def _row_buffers(self) -> _RowParams:
+        if self.rowp is None:
+            self.rowp = _RowParams(self.max_batch, self.device)
+        return self.rowp
 
     def _check_lookup(self, params: SamplingParams):
         K, n = params.lookup_tokens, params.lookup_ngram
@@ -249,11 +327,26 @@ class Generator:
         (the decode step's row bucket, or one row admitted by continuous batching)."""
         r1 = r0 + h.shape[0]
         logits = self.model.logits(h)
-        ops.sample(logits, params.inv_temp, params.top_k, params.top_p, params.greedy, params.seed,
-                   self.rng_offset, self.active[r0:r1], self.sampled[r0:r1], self.sampled_lp[r0:r1])
+        rp = self.rowp if self._rows_on else None
+        if rp is not None:
+            # the row's own settings and stream: (seed, tokens generated so far) key the draw
+            ops.sample_rows(logits, rp.inv_temp[r0:r1], rp.top_k[r0:r1], rp.top_p[r0:r1], rp.greedy[r0:r1],
+                            rp.seed[r0:r1], self.gen_len[r0:r1], self.active[r0:r1], self.sampled[r0:r1],
+                            self.sampled_lp[r0:r1])
+        else:
+            ops.sample(logits, params.inv_temp, params.top_k, params.top_p, params.greedy, params.seed,
+                       self.rng_offset, self.active[r0:r1], self.sampled[r0:r1], self.sampled_lp[r0:r1])
         if self.value_head is not None:
             self.values[r0:r1].copy_(self.value_head(h))
-        if h.is_cuda:
+        if h.is_cuda and rp is not None:
+            vh = self.value_head is not None
+            ops.native().decode_update_rows(self.sampled[r0:r1], self.out_tokens[r0:r1], self.out_logp[r0:r1],
+                                            self.sampled_lp[r0:r1], self.out_values[r0:r1] if vh else None,
+                                            self.values[r0:r1] if vh else None, self.active[r0:r1],
+                                            self.kv_len[r0:r1], self.pos[r0:r1], self.tok_in[r0:r1],
+                                            self.gen_len[r0:r1], self.step, self.rng_offset, eos_ids, pad_id,
+                                            self.attn_len[r0:r1], self.kv_start[r0:r1], rp.max_new[r0:r1])
+        elif h.is_cuda:
             vh = self.value_head is not None
             ops.native().decode_update(self.sampled[r0:r1], self.out_tokens[r0:r1], self.out_logp[r0:r1],
                                        self.sampled_lp[r0:r1], self.out_values[r0:r1] if vh else None,
@@ -272,6 +365,8 @@ class Generator:
         act = self.active[r0:r1].bool()
         gl = self.gen_len[r0:r1]
         act = act & (gl < T)
+        # the row's own answer length under per-request sampling
+        lim = self.rowp.max_new[r0:r1].clamp(max=T) if self._rows_on else T
         rows = torch.nonzero(act).flatten()
         if rows.numel():
             idx = gl[rows].long()
@@ -280,7 +375,7 @@ class Generator:
             self.out_logp[r0 + rows, idx] = self.sampled_lp[r0:r1][rows]
             if self.value_head is not None:
                 self.out_values[r0 + rows, idx] = self.values[r0:r1][rows]
-            fin = torch.isin(samp, eos_ids) | (gl + 1 >= T)
+            fin = torch.isin(samp, eos_ids) | (gl + 1 >= lim)
             gl[act] += 1
             self.kv_len[r0:r1][act] += 1
             self.tok_in[r0:r1].copy_(torch.where(act, samp, torch.full_like(samp, pad_id)))
@@ -327,6 +422,7 @@ class Generator:
         if params.max_length is not None:
             T = max(1, min(T, params.max_length - S))
         self._check_lookup(params)
+        self._rows_on = False  # a batch under one SamplingParams: the scalar sampler and its stream
         K = params.lookup_tokens
         # the last verify step may append K rows past the last emitted token
         assert S + T + K <= self.max_seq, f"prompt {S} + new {T} (+ {K} draft) exceeds cache {self.max_seq}"
@@ -429,6 +525,9 @@ class Generator:
         key = (T, params.inv_temp, params.top_k, params.top_p, params.greedy, params.seed, tuple(eos_list), pad_id,
                self._nb)
         step = self._step
+        if self._rows_on:
+            # parameters are read from the row buffers: one graph per bucket whatever the mix
+            key = (T, "rows", tuple(eos_list), pad_id, self._nb)
         if _fp4_decode_on(self.model):
             key = key + ("fp4",)  # the captured step of the other setting streams other weight images
         if self._lk is not None:
@@ -453,6 +552,8 @@ class Generator:
               self.out_values]
         if self._lk is not None:
             st += [self.hist] + self._lk.tensors()
+        if self.rowp is not None:
+            st += self.rowp.tensors()
         return st
 
 
@@ -644,6 +745,7 @@ class FinishedRow:
     logprobs: List[float]
     prompt_len: int
     steps_waited: int
+    seed: Optional[int] = None  # per-request sampling: the seed the row drew with (given or derived)
 
 
 class ContinuousBatcher:
@@ -654,13 +756,23 @@ class ContinuousBatcher:
     own output position (``decode_update_kernel`` indexes by the row's generated length) and
     leaves the batch when it emits EOS or reaches ``max_new_tokens``, freeing the row for the next
     request. Rows are independent: other rows' K/V, positions and attention lengths are untouched
-    by an admission. One sampling configuration per batcher; the decode step runs the
-    power-of-two bucket of rows that covers the active ones (inactive rows in it are masked).
+    by an admission. One sampling configuration per batcher unless ``per_request``; the decode
+    step runs the power-of-two bucket of rows that covers the active ones (inactive rows in it are
+    masked).
+
+    ``per_request=True``: every admission may bring a ``RequestSampling`` (temperature, top-k, top-p,
+    greedy or sampled, seed, answer length). The settings live in per-row device buffers that the
+    captured step reads (``ops.sample_rows``, the per-row bookkeeping limit), so one graph per bucket
+    serves any mix, and a row's random stream is keyed by (its seed, its generated length): the
+    same request draws the same answer in any row, beside any batch mates, at any time. A request
+    without a seed gets ``derive_seed(params.seed, admission count)``; ``FinishedRow.seed`` reports
+    it. With ``per_request=False`` graph keys and the RNG stream are the scalar sampler's.
 
     Usage: ``admit(prompt_ids, tag)`` while ``free_rows()``; ``step(n)``; ``collect()`` returns the
     rows that finished (a host read of the per-row flags once per call)."""
 
-    def __init__(self, gen: Generator, params: SamplingParams, pad_id: int = 0, eos_ids: Sequence[int] = ()):
+    def __init__(self, gen: Generator, params: SamplingParams, pad_id: int = 0, eos_ids: Sequence[int] = (),
+                 per_request: bool = False):
         if params.lookup_tokens > 0:
             raise NotImplementedError("prompt-lookup decoding is not supported with continuous batching")
         if _fp4_decode_on(gen.model) and gen.max_batch > 16:
@@ -685,6 +797,13 @@ class ContinuousBatcher:
             g.out_values = torch.zeros(MB, T, dtype=torch.float32, device=dev)
             g.runner.reset()
         g._nb = 1
+        self.per_request = bool(per_request)
+        g._rows_on = self.per_request
+        self.admitted = 0   # admission count: numbers the derived seeds
+        self.row_seed = {}  # row -> seed (per_request)
+        if self.per_request:
+            # every row starts at the batcher's defaults (the capture below runs the step on them)
+            g._row_buffers().write(0, [RequestSampling().resolve(params, T, 0)] * MB)
         self._prev_merged = g.model.set_lora_merged(g.merge_lora) if hasattr(g.model, "set_lora_merged") else None
         if hasattr(g.model, "refresh_decode_weights"):
             g.model.refresh_decode_weights(MB)
@@ -695,6 +814,7 @@ class ContinuousBatcher:
         self.steps = 0
 
     def close(self):
+        self.gen._rows_on = False
         if self._prev_merged is not None:
             self.gen.model.set_lora_merged(self._prev_merged)
             self._prev_merged = None
@@ -706,35 +826,49 @@ class ContinuousBatcher:
         return len(self.rows)
 
     @torch.no_grad()
-    def admit(self, prompt: List[int], tag=None) -> int:
-        return self.admit_many([prompt], [tag])[0]
+    def admit(self, prompt: List[int], tag=None, sampling: Optional[RequestSampling] = None) -> int:
+        return self.admit_many([prompt], [tag], [sampling])[0]
 
     @torch.no_grad()
-    def admit_many(self, prompts: List[List[int]], tags=None) -> List[int]:
+    def admit_many(self, prompts: List[List[int]], tags=None, sampling=None) -> List[int]:
         """Admit len(prompts) <= free_rows() requests. The lowest free rows are taken and every run
-        of consecutive rows is prefilled as ONE left-padded batch into its cache rows."""
+        of consecutive rows is prefilled as ONE left-padded batch into its cache rows.
+        ``sampling``: one ``RequestSampling`` or None per prompt (``per_request`` batchers only)."""
         g = self.gen
         tags = list(tags) if tags is not None else [None] * len(prompts)
+        sampling = list(sampling) if sampling is not None else [None] * len(prompts)
+        if len(sampling) != len(prompts):
+            raise ValueError(f"{len(sampling)} sampling entries for {len(prompts)} prompts")
+        if not self.per_request and any(s is not None for s in sampling):
+            raise ValueError("per-request sampling settings need ContinuousBatcher(per_request=True)")
         if len(prompts) > len(self.free):
             raise ValueError(f"{len(prompts)} requests for {len(self.free)} free rows")
+        resolved = None
+        if self.per_request:
+            # validated before any row is taken; unseeded requests are numbered by admission
+            resolved = [(s or RequestSampling()).resolve(self.params, self.T, derive_seed(self.params.seed,
+                                                                                         self.admitted + i))
+                        for i, s in enumerate(sampling)]
         for p in prompts:
             if len(p) < 1 or len(p) + self.T > g.max_seq:
                 raise ValueError(f"prompt of {len(p)} tokens + {self.T} new exceeds the cache ({g.max_seq})")
         self.free.sort()
         rows, self.free = self.free[:len(prompts)], self.free[len(prompts):]
         try:
-            self._admit_runs(rows, prompts, tags)
+            self._admit_runs(rows, prompts, tags, resolved)
         except BaseException:
             # all-or-nothing: rows of this call that were already prefilled leave the batch again
             # (inactive, back on the free list), so the caller can fail every request it passed
             for b in rows:
                 self.rows.pop(b, None)
+                self.row_seed.pop(b, None)
             g.active[torch.tensor(rows, device=g.device)] = 0
             self.free = sorted(self.free + rows)
             raise
+        self.admitted += len(prompts)
         return rows
 
-    def _admit_runs(self, rows, prompts, tags):
+    def _admit_runs(self, rows, prompts, tags, resolved=None):
         g = self.gen
         i = 0
         while i < len(rows):
@@ -755,9 +889,13 @@ class ContinuousBatcher:
             g.kv_len[b0:b0 + n].fill_(S - 1)  # the first bookkeeping advances them to S
             g.gen_len[b0:b0 + n].zero_()
             g.active[b0:b0 + n].fill_(1)
+            if resolved is not None:
+                g.rowp.write(b0, resolved[i:j])
             g._emit(h_last, self.params, self.eos, self.pad_id, r0=b0)
             for r in range(n):
                 self.rows[b0 + r] = (tags[i + r], len(grp[r]), self.steps)
+                if resolved is not None:
+                    self.row_seed[b0 + r] = resolved[i + r][4]
             i = j
 
     def step(self, n: int = 1):
@@ -788,6 +926,7 @@ class ContinuousBatcher:
             lps = g.out_logp.index_select(0, idx).cpu()
             for b, n, t, lp in zip(done, lens, toks, lps):
                 tag, S, s0 = self.rows.pop(b)
-                out.append(FinishedRow(tag, t[:n].tolist(), lp[:n].tolist(), S, self.steps - s0))
+                out.append(FinishedRow(tag, t[:n].tolist(), lp[:n].tolist(), S, self.steps - s0,
+                                       self.row_seed.pop(b, None)))
                 self.free.append(b)
         return out

@@ -12,7 +12,7 @@ from .attention import (  # noqa: F401
     flash_attention_qkv, rope_qkv, rope_qkv_, FP8_KV_D, kv_dequantize, kv_quantize_rows, kv_store_fp8,
     verify_step_attention,
 )
-from .misc import (embedding, gae, ivf_scan, ppo_advantages, pool_normalize, ppo_loss, row_dot, sample, segment_mean,  # noqa: F401
+from .misc import (embedding, gae, ivf_scan, ppo_advantages, pool_normalize, ppo_loss, row_dot, sample, sample_rows, segment_mean,  # noqa: F401
                    swiglu, token_logprobs, topk, lookup_accept, lookup_draft)
 from .optim import FlatParams, FusedAdamW, MixedFlatParams, flat_params  # noqa: F401
 from .fp8 import Fp8Cache, dequantize_fp8, gemm_fp8, quantize_fp8  # noqa: F401

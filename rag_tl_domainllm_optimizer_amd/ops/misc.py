@@ -150,6 +150,30 @@ def sample(logits, inv_temp=1.0, top_k=0, top_p=1.0, greedy=False, seed=0, offse
     return out_tok, out_logp
 
 
+def sample_rows(logits, inv_temp, top_k, top_p, greedy, seed, counter, active=None, out_tok=None, out_logp=None):
+    """``sample`` with per-row parameters, every one a [B] tensor on the logits' device: inv_temp
+    f32, top_k i32 (0 = off), top_p f32, greedy u8, seed i64, counter i32. On the GPU the kernels
+    read them from memory (a captured graph sees new values on replay) and row b draws from the
+    Philox stream (seed[b], counter[b]) — what ``sample`` draws for that row alone with
+    ``seed = seed[b]`` and ``offset = [counter[b]]``. Returns (tokens int64 [B], logp [B])."""
+    B = logits.shape[0]
+    if not on_gpu(logits):
+        tok, lp = ref.sample_rows(logits, inv_temp, top_k, top_p, greedy, seed, counter, active)
+        if out_tok is not None:
+            out_tok.copy_(tok)
+            tok = out_tok
+        if out_logp is not None:
+            out_logp.copy_(lp)
+            lp = out_logp
+        return tok, lp
+    if out_tok is None:
+        out_tok = torch.empty(B, dtype=torch.long, device=logits.device)
+    if out_logp is None:
+        out_logp = torch.empty(B, dtype=torch.float32, device=logits.device)
+    native().sample_rows(logits, inv_temp, top_k, top_p, greedy, seed, counter, active, out_tok, out_logp)
+    return out_tok, out_logp
+
+
 # ------------------------------------------------- prompt-lookup speculative decoding bookkeeping
 def lookup_accept(sampled, logp, inp, n_draft, out_tokens, out_logp, hist, active, kv_len, pos, attn_len, kv_start,
                   gen_len, step, rng_offset, counters, eos_ids):

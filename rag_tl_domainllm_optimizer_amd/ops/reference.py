@@ -206,6 +206,25 @@ def sample(logits, inv_temp=1.0, top_k=0, top_p=1.0, greedy=False, generator=Non
     return tok, x.gather(1, tok[:, None])[:, 0] - lse
 
 
+def sample_rows(logits, inv_temp, top_k, top_p, greedy, seed, counter, active=None):
+    """Per-row parameters ([B] each): row b is filtered by ``filter_logits`` with its own settings
+    and drawn from a generator seeded from (seed[b], counter[b]) alone, so the draw does not depend
+    on the row's place or its batch mates. Greedy and inactive rows return the argmax."""
+    x = logits.float() * inv_temp.float()[:, None]
+    lse = torch.logsumexp(x, -1)
+    tok = x.argmax(-1)
+    for b in range(logits.shape[0]):
+        if bool(greedy[b]) or (active is not None and not bool(active[b])):
+            continue
+        keep = filter_logits(logits[b:b + 1], float(inv_temp[b]), int(top_k[b]), float(top_p[b]))
+        probs = torch.softmax(x[b:b + 1].masked_fill(~keep, float("-inf")), -1)
+        g = torch.Generator(device="cpu")
+        # one 64-bit generator seed per (seed, counter): a multiplicative mix keeps nearby pairs apart
+        g.manual_seed((int(seed[b]) * 0x9E3779B97F4A7C15 + int(counter[b]) * 0xBF58476D1CE4E5B9 + 1) % (1 << 63))
+        tok[b] = torch.multinomial(probs.cpu(), 1, generator=g)[0, 0]
+    return tok, x.gather(1, tok[:, None])[:, 0] - lse
+
+
 def pool_norm(x, lengths=None, normalize=True):
     B, S, H = x.shape
     xf = x.float()

@@ -1,6 +1,9 @@
 """HTTP answer service (the README's optional frontend, README.md:9,31: Streamlit / Gradio are not
 installed; FastAPI + uvicorn are). POST /answer {"query": "...", "top_k": 3} ->
 {"answer", "doc_ids", "docs", "scores", "timings"}; GET /health; GET /stats.
+With ``per_request_sampling`` (config ``serve.per_request_sampling``, continuous batching only) the
+body may also carry ``temperature``, ``top_k_tokens``, ``top_p``, ``do_sample``, ``seed`` and
+``max_new_tokens``; ``timings["seed"]`` returns the seed the answer was drawn with.
 
 Concurrent requests are batched: the async handler awaits a future while one worker thread owns the
 GPU — by default ``serve.continuous.ContinuousEngine`` (requests join the running decode batch
@@ -13,24 +16,51 @@ from .batching import BatchingEngine  # noqa: F401
 from .continuous import ContinuousEngine  # noqa: F401
 
 
-def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False):
+SAMPLING_FIELDS = ("temperature", "top_k_tokens", "top_p", "do_sample", "seed", "max_new_tokens")
+
+
+def request_sampling(q, max_new_tokens: Optional[int] = None):
+    """The ``RequestSampling`` of an /answer body (None when it sets no sampling field); ValueError
+    for a value outside its range. ``top_k`` stays the document count: the token top-k is
+    ``top_k_tokens``."""
+    from ..generation import RequestSampling
+
+    vals = {f: getattr(q, f, None) for f in SAMPLING_FIELDS}
+    if all(v is None for v in vals.values()):
+        return None
+    rs = RequestSampling(temperature=vals["temperature"], top_k=vals["top_k_tokens"], top_p=vals["top_p"],
+                         do_sample=vals["do_sample"], seed=vals["seed"], max_new_tokens=vals["max_new_tokens"])
+    rs.validate(max_new_tokens)
+    return rs
+
+
+def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, per_request_sampling: bool = False):
     import asyncio
 
-    from fastapi import FastAPI
+    from fastapi import FastAPI, HTTPException
     from pydantic import BaseModel
 
-    engine = ContinuousEngine(pipeline) if continuous else BatchingEngine(pipeline, max_wait_s=max_wait_s)
+    if per_request_sampling and not continuous:
+        raise ValueError("per_request_sampling needs continuous batching (continuous=True)")
+    engine = ContinuousEngine(pipeline, per_request_sampling=per_request_sampling) if continuous else \
+        BatchingEngine(pipeline, max_wait_s=max_wait_s)
     app = FastAPI(title="rag-tl-domainllm-optimizer-amd")
     app.state.engine = engine
 
     class Query(BaseModel):
         query: str
-        top_k: Optional[int] = None
+        top_k: Optional[int] = None  # retrieved documents
+        temperature: Optional[float] = None
+        top_k_tokens: Optional[int] = None
+        top_p: Optional[float] = None
+        do_sample: Optional[bool] = None
+        seed: Optional[int] = None
+        max_new_tokens: Optional[int] = None
 
     @app.get("/health")
     def health():
         return {"status": "ok", "docs": len(pipeline.docs), "max_batch": pipeline.max_batch,
-                "batching": "continuous" if continuous else "dynamic"}
+                "batching": "continuous" if continuous else "dynamic", "per_request_sampling": per_request_sampling}
 
     @app.get("/stats")
     def stats():
@@ -38,7 +68,15 @@ def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False):
 
     @app.post("/answer")
     async def answer(q: Query):
-        a = await asyncio.wrap_future(engine.submit(q.query, q.top_k))
+        try:
+            rs = request_sampling(q, getattr(getattr(pipeline, "sampling", None), "max_new_tokens", None))
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e))
+        if rs is not None and not per_request_sampling:
+            raise HTTPException(status_code=400, detail="sampling settings in the request need the server flag "
+                                                        "serve.per_request_sampling (off on this server)")
+        a = await asyncio.wrap_future(engine.submit(q.query, q.top_k, rs) if rs is not None else
+                                      engine.submit(q.query, q.top_k))
         return {"answer": a.answer, "doc_ids": a.doc_ids, "docs": a.docs, "scores": a.scores, "timings": a.timings}
 
     @app.on_event("shutdown")
@@ -49,7 +87,7 @@ def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False):
 
 
 def serve(cfg, host: str = "127.0.0.1", port: int = 8000, max_batch: int = 16, max_wait_s: float = 0.004,
-          continuous: bool = True):
+          continuous: bool = True, per_request_sampling: Optional[bool] = None):
     import uvicorn
 
     from ..cli import apply_fp4, build_stack
@@ -64,4 +102,6 @@ def serve(cfg, host: str = "127.0.0.1", port: int = 8000, max_batch: int = 16, m
                         do_sample=cfg.eval.do_sample, top_k=cfg.eval.top_k)
     rag = RagPipeline(st["encoder"], st["index"], st["docs"], st["policy"], st["tokenizer"], cfg.retrieval.top_k, sp,
                       cfg.ppo.max_prompt_tokens, max_batch=max_batch)
-    uvicorn.run(create_app(rag, max_wait_s, continuous), host=host, port=port)
+    if per_request_sampling is None:
+        per_request_sampling = cfg.serve.per_request_sampling
+    uvicorn.run(create_app(rag, max_wait_s, continuous, per_request_sampling), host=host, port=port)

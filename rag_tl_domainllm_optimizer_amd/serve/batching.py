@@ -31,7 +31,11 @@ class BatchingEngine:
         self._worker.start()
 
     # ---------------------------------------------------------------- client side
-    def submit(self, query: str, top_k: Optional[int] = None) -> cf.Future:
+    def submit(self, query: str, top_k: Optional[int] = None, sampling=None) -> cf.Future:
+        if sampling is not None:
+            # a request group runs to completion under the pipeline's one SamplingParams
+            raise ValueError("BatchingEngine does not support per-request sampling settings; use "
+                             "ContinuousEngine(per_request_sampling=True)")
         if self._closed:
             raise RuntimeError("BatchingEngine is closed")
         fut: cf.Future = cf.Future()

@@ -10,6 +10,11 @@ the batch stays full under load.
 Same client API as ``BatchingEngine``: ``submit`` -> Future[RagAnswer], ``answer``, ``answer_many``,
 ``close``. ``timings``: ``queue_s`` (submit -> admission), ``total_s`` (submit -> answer),
 ``retrieve_s``, ``new_tokens``, ``prompt_tokens``, ``decode_steps`` (steps the row was in flight).
+
+``per_request_sampling=True``: ``submit(..., sampling=RequestSampling(...))`` gives a request its own
+temperature, top-k, top-p, greedy flag, seed and answer length inside the shared batch
+(``ContinuousBatcher(per_request=True)``); ``timings["seed"]`` is the seed the answer was drawn
+with, so a client can ask for the same answer again.
 """
 from __future__ import annotations
 
@@ -21,13 +26,13 @@ from typing import List, Optional
 
 import torch
 
-from ..generation import ContinuousBatcher
+from ..generation import ContinuousBatcher, RequestSampling
 from ..rag.pipeline import RagAnswer
 from ..rag.prompt import extract_answer
 
 
 class ContinuousEngine:
-    def __init__(self, pipeline, chunk: int = 4):
+    def __init__(self, pipeline, chunk: int = 4, per_request_sampling: bool = False):
         if pipeline.sampling.lookup_tokens > 0:
             raise NotImplementedError("prompt-lookup decoding is not supported with continuous batching")
         layers = getattr(pipeline.gen.model, "layers", None)
@@ -36,6 +41,7 @@ class ContinuousEngine:
                              f"exceeds the 16 rows of the MXFP4 decode kernels")
         self.pipeline = pipeline
         self.chunk = max(1, chunk)
+        self.per_request_sampling = bool(per_request_sampling)
         self._q: "queue.Queue" = queue.Queue()
         self._closed = False
         self._dead: Optional[BaseException] = None  # the error that ended the worker, if any
@@ -51,22 +57,28 @@ class ContinuousEngine:
             raise self._init_error
 
     # ---------------------------------------------------------------- client side
-    def submit(self, query: str, top_k: Optional[int] = None) -> cf.Future:
+    def submit(self, query: str, top_k: Optional[int] = None,
+               sampling: Optional[RequestSampling] = None) -> cf.Future:
+        if sampling is not None:
+            if not self.per_request_sampling:
+                raise ValueError("per-request sampling settings need ContinuousEngine(per_request_sampling=True)")
+            sampling.validate(self.pipeline.sampling.max_new_tokens)
         with self._lock:
             if self._closed:
                 if self._dead is not None:
                     raise RuntimeError(f"ContinuousEngine worker failed: {self._dead!r}") from self._dead
                 raise RuntimeError("ContinuousEngine is closed")
             fut: cf.Future = cf.Future()
-            self._q.put((query, top_k, fut, time.perf_counter()))
+            self._q.put((query, top_k, fut, time.perf_counter(), sampling))
         return fut
 
     @property
     def alive(self) -> bool:
         return not self._closed and self._worker.is_alive()
 
-    def answer(self, query: str, top_k: Optional[int] = None, timeout: Optional[float] = None) -> RagAnswer:
-        return self.submit(query, top_k).result(timeout)
+    def answer(self, query: str, top_k: Optional[int] = None, timeout: Optional[float] = None,
+               sampling: Optional[RequestSampling] = None) -> RagAnswer:
+        return self.submit(query, top_k, sampling).result(timeout)
 
     def answer_many(self, queries: List[str], timeout: Optional[float] = None) -> List[RagAnswer]:
         futs = [self.submit(q) for q in queries]
@@ -102,7 +114,7 @@ class ContinuousEngine:
                 it[2].set_exception(e)
             return
         t1 = time.perf_counter()
-        prompts, metas = [], []
+        prompts, metas, samplings = [], [], []
         for it, row_ids, row_sc in zip(live, ids_l, sc_l):
             docs = [p.docs[i] for i in row_ids if i >= 0]
             prompt = p._prompt_ids(it[0], docs)
@@ -110,13 +122,15 @@ class ContinuousEngine:
                 it[2].set_exception(ValueError("prompt does not fit the serving cache"))
                 continue
             prompts.append(prompt)
+            samplings.append(it[4])
             metas.append({"query": it[0], "fut": it[2], "t_submit": it[3], "t_admit": time.perf_counter(),
                           "retrieve_s": t1 - t0, "doc_ids": row_ids, "docs": docs, "scores": row_sc,
                           "rows0": (self._row_steps, self.stats["steps"])})
         if not prompts:
             return
         try:
-            cb.admit_many(prompts, metas)  # consecutive free rows share one prefill
+            # consecutive free rows share one prefill
+            cb.admit_many(prompts, metas, samplings if self.per_request_sampling else None)
         except BaseException as e:  # noqa: BLE001
             for m in metas:
                 m["fut"].set_exception(e)
@@ -137,13 +151,16 @@ class ContinuousEngine:
                    "total_s": now - m["t_submit"], "new_tokens": len(r.tokens), "prompt_tokens": r.prompt_len,
                    "decode_steps": r.steps_waited,
                    "batch_size": (self._row_steps - rs0) / steps if steps > 0 else 0.0}
+            if r.seed is not None:
+                tim["seed"] = r.seed
             m["fut"].set_result(RagAnswer(m["query"], text, m["doc_ids"], m["docs"], m["scores"], tim))
             self.stats["finished"] += 1
 
     def _loop(self):
         p = self.pipeline
         try:
-            cb = ContinuousBatcher(p.gen, p.sampling, pad_id=p.tok.pad_token_id, eos_ids=[p.tok.eos_token_id])
+            cb = ContinuousBatcher(p.gen, p.sampling, pad_id=p.tok.pad_token_id, eos_ids=[p.tok.eos_token_id],
+                                   per_request=self.per_request_sampling)
         except BaseException as e:  # noqa: BLE001
             self._init_error = e
             self._ready.set()
