@@ -42,6 +42,11 @@ int rt_quant_mxfp4(const void*, void*, void*, long, long, hipStream_t);
 int rt_shuffle_decode_weight_fp4(const void*, const void*, void*, void*, long, long, hipStream_t);
 int rt_gemv_fp4(const void*, long, const void*, const void*, const void*, void*, long, int, int, int, int, int,
                 const void*, long, float, hipStream_t);
+int rt_lora_rows_slices(int);
+int rt_lora_rows_shrink(const void*, long, const void*, const int*, float*, int, int, int, int, int, hipStream_t);
+int rt_gemv16_rows_lora(int, const void*, long, const void*, const void*, const float*, void*, long, int, int, int, int,
+                        const void*, long, float, const float*, const void*, const int*, int, int, int, int, int, int,
+                        hipStream_t);
 int rt_norm_fwd(int, const void*, const void*, const void*, const void*, void*, void*, float*, float*, int, int, float,
                 const float*, int, hipStream_t);
 int rt_norm_bwd(int, const void*, const void*, const void*, const float*, const float*, const void*, void*, float*,
@@ -753,6 +758,104 @@ Tensor gemv_fp4(const Tensor& a, const Tensor& img, const Tensor& simg, const op
                        has_res ? residual->data_ptr() : nullptr, has_res ? residual->stride(0) : 0, (float)norm_eps,
                        cur_stream()),
            "gemv_fp4");
+  return c;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Per-row LoRA adapters of a decode step (M <= 16). Shrink: T [ks, 16, RT] fp32 = the K-slice slabs of
+// a_img[ids[b]] x[b] (a_img [slots, RT, K] bf16, RT = nseg R; ids int32 [>= M], < 0 = no adapter).
+Tensor lora_rows_shrink(const Tensor& x, const Tensor& a_img, const Tensor& ids, int64_t ks, optional<Tensor> out) {
+  CHECK_CUDA(x); CHECK_CUDA(a_img); CHECK_CUDA(ids); CHECK_BF16(x); CHECK_BF16(a_img); CHECK_I32(ids);
+  CHECK_ROWS(x); CHECK_ALIGN16(x); CHECK_ALIGN16(a_img);
+  TORCH_CHECK(a_img.dim() == 3 && a_img.is_contiguous() && ids.is_contiguous(), "lora_rows_shrink: contiguous a_img [slots, RT, K]");
+  TORCH_CHECK(a_img.device() == x.device() && ids.device() == x.device(), "lora_rows_shrink: operands on different devices");
+  const int64_t M = x.size(0), K = x.size(1), slots = a_img.size(0), RT = a_img.size(1);
+  TORCH_CHECK(M <= 16, "lora_rows_shrink: at most 16 rows");
+  TORCH_CHECK(ids.numel() >= M, "lora_rows_shrink: ids shorter than the batch");
+  TORCH_CHECK(a_img.size(2) == K && K > 0 && K % 64 == 0 && RT > 0 && RT % 8 == 0 && RT <= 192 && slots > 0,
+              "lora_rows_shrink: needs K % 64 == 0, RT % 8 == 0, RT <= 192");
+  TORCH_CHECK(M <= 1 || x.stride(0) % 8 == 0, "lora_rows_shrink: row stride of x must be a multiple of 8");
+  if (ks <= 0) ks = rt_lora_rows_slices((int)K);
+  TORCH_CHECK(ks <= 64, "lora_rows_shrink: at most 64 K slices");
+  Tensor t = (out.has_value() && out->defined()) ? *out : at::empty({ks, 16, RT}, x.options().dtype(at::kFloat));
+  TORCH_CHECK(t.is_cuda() && t.device() == x.device() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.dim() == 3 &&
+                  t.size(0) == ks && t.size(1) == 16 && t.size(2) == RT, "lora_rows_shrink: out must be fp32 [ks, 16, RT]");
+  CHECK_ALIGN16(t);
+  if (M == 0) return t;
+  check_rc(rt_lora_rows_shrink(x.data_ptr(), M == 1 ? 0 : x.stride(0), a_img.data_ptr(), ids.data_ptr<int>(),
+                               t.data_ptr<float>(), (int)M, (int)K, (int)RT, (int)slots, (int)ks, cur_stream()),
+           "lora_rows_shrink");
+  return t;
+}
+
+// The 16-row kernel with the per-row adapter term in its tail: fmt 0 = w the tile-ordered bf16 image
+// [N, K], 1 = w the fp8 image [N, K] bytes + aux the per-column scales [N] fp32, 2 = w the MXFP4 code
+// image [N, K / 2] + aux the scale image [N, K / 32]. t = lora_rows_shrink's slabs, b_img [slots, N,
+// R] bf16, seg1 / seg2 = first output column of segments 1 / 2 (>= N: none).
+Tensor gemv16_rows_lora(int64_t fmt, const Tensor& a, const Tensor& w, const optional<Tensor>& aux, int64_t act,
+                        const optional<Tensor>& residual, double norm_eps, const Tensor& t, const Tensor& b_img,
+                        const Tensor& ids, int64_t seg1, int64_t seg2, optional<Tensor> out) {
+  CHECK_CUDA(a); CHECK_CUDA(w); CHECK_CUDA(t); CHECK_CUDA(b_img); CHECK_CUDA(ids);
+  CHECK_BF16(a); CHECK_ROWS(a); CHECK_ALIGN16(a); CHECK_ALIGN16(w); CHECK_BF16(b_img); CHECK_I32(ids); CHECK_F32(t);
+  CHECK_ALIGN16(t); CHECK_ALIGN16(b_img);
+  TORCH_CHECK(fmt >= 0 && fmt <= 2, "gemv16_rows_lora: fmt 0 (bf16), 1 (fp8) or 2 (MXFP4)");
+  TORCH_CHECK(w.dim() == 2 && w.is_contiguous() && t.dim() == 3 && t.is_contiguous() && b_img.dim() == 3 &&
+                  b_img.is_contiguous() && ids.is_contiguous(), "gemv16_rows_lora: contiguous operands expected");
+  const int64_t M = a.size(0), K = a.size(1), N = w.size(0), S = fmt == 0 ? 1 : fmt == 1 ? 2 : 4;
+  const bool pair = act == 5;
+  TORCH_CHECK(M <= 16, "gemv16_rows_lora: per-row adapters run at most 16 rows");
+  TORCH_CHECK(act >= 0 && act <= 5, "gemv16_rows_lora: unknown activation");
+  TORCH_CHECK(K > 0 && K % (64 * S) == 0 && N > 0 && N % (pair ? 64 : 16) == 0, "gemv16_rows_lora: needs K % (64 S) == 0, N % 16 == 0");
+  TORCH_CHECK(M <= 1 || a.stride(0) % 8 == 0, "gemv16_rows_lora: row stride of a must be a multiple of 8");
+  const float* sb = nullptr;
+  const void* simg = nullptr;
+  if (fmt == 0) {
+    CHECK_BF16(w);
+    TORCH_CHECK(w.size(1) == K, "gemv16_rows_lora: bf16 image [N, K]");
+  } else if (fmt == 1) {
+    TORCH_CHECK(w.element_size() == 1 && w.size(1) == K, "gemv16_rows_lora: fp8 image [N, K] bytes");
+    TORCH_CHECK(aux.has_value() && aux->defined() && aux->is_cuda() && aux->scalar_type() == at::kFloat &&
+                    aux->numel() == N && aux->is_contiguous(), "gemv16_rows_lora: fp8 needs column scales [N] fp32");
+    sb = aux->data_ptr<float>();
+  } else {
+    TORCH_CHECK(w.scalar_type() == at::kByte && w.size(1) == K / 2, "gemv16_rows_lora: MXFP4 code image [N, K / 2]");
+    TORCH_CHECK(aux.has_value() && aux->defined() && aux->is_cuda() && aux->scalar_type() == at::kByte && aux->dim() == 2 &&
+                    aux->size(0) == N && aux->size(1) == K / 32 && aux->is_contiguous() &&
+                    reinterpret_cast<uintptr_t>(aux->data_ptr()) % 2 == 0, "gemv16_rows_lora: MXFP4 needs the scale image [N, K / 32]");
+    simg = aux->data_ptr();
+  }
+  const int64_t slots = b_img.size(0), R = b_img.size(2), ks = t.size(0), RT = t.size(2);
+  TORCH_CHECK(b_img.size(1) == N && (R == 8 || R == 16 || R == 32 || R == 64), "gemv16_rows_lora: b_img [slots, N, R], R in {8, 16, 32, 64}");
+  TORCH_CHECK(t.size(1) == 16 && RT % R == 0 && RT / R >= 1 && RT / R <= 3 && RT <= 192 && ks >= 1,
+              "gemv16_rows_lora: t [ks, 16, nseg R] with nseg <= 3, nseg R <= 192");
+  const int64_t nseg = RT / R;
+  TORCH_CHECK(ids.numel() >= M, "gemv16_rows_lora: ids shorter than the batch");
+  if (pair) {
+    TORCH_CHECK(nseg == 2, "gemv16_rows_lora: the SwiGLU pair has two segments (gate | up)");
+  } else {
+    // a column's segment index must stay below nseg
+    TORCH_CHECK(seg1 > 0 && seg1 <= seg2 && (nseg > 1 || seg1 >= N) && (nseg > 2 || seg2 >= N),
+                "gemv16_rows_lora: segment bounds do not match t");
+  }
+  const int64_t Nout = pair ? N / 2 : N;
+  Tensor c = (out.has_value() && out->defined()) ? *out : at::empty({M, Nout}, a.options().dtype(at::kBFloat16));
+  TORCH_CHECK(c.is_cuda() && c.device() == a.device() && c.dim() == 2 && c.size(0) == M && c.size(1) == Nout &&
+                  c.stride(1) == 1 && c.scalar_type() == at::kBFloat16, "gemv16_rows_lora: out");
+  if (M == 0) return c;
+  const bool has_res = residual.has_value() && residual->defined();
+  if (has_res) {
+    CHECK_CUDA(*residual); CHECK_BF16(*residual);
+    TORCH_CHECK(!pair, "gemv16_rows_lora: no residual in SwiGLU pair mode");
+    TORCH_CHECK(residual->dim() == 2 && residual->size(0) == M && residual->size(1) == Nout && residual->stride(1) == 1,
+                "gemv16_rows_lora: residual shape");
+  }
+  const int big = 1 << 30;
+  check_rc(rt_gemv16_rows_lora((int)fmt, a.data_ptr(), M == 1 ? 0 : a.stride(0), w.data_ptr(), simg, sb, c.data_ptr(),
+                               c.stride(0), (int)M, (int)N, (int)K, (int)act, has_res ? residual->data_ptr() : nullptr,
+                               has_res ? residual->stride(0) : 0, (float)norm_eps, t.data_ptr<float>(), b_img.data_ptr(),
+                               ids.data_ptr<int>(), (int)R, (int)nseg, (int)ks, (int)std::min<int64_t>(seg1, big),
+                               (int)std::min<int64_t>(seg2, big), (int)slots, cur_stream()),
+           "gemv16_rows_lora");
   return c;
 }
 
@@ -1583,6 +1686,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemv_fp4", &gemv_fp4, "W4A16 decode GEMV (M <= 16) on the MXFP4 image", py::arg("a"), py::arg("img"),
         py::arg("simg"), py::arg("bias") = py::none(), py::arg("act") = 0, py::arg("out_f32") = false,
         py::arg("out") = py::none(), py::arg("residual") = py::none(), py::arg("norm_eps") = 0.0);
+  m.def("lora_rows_shrink", &lora_rows_shrink, "per-row adapter shrink (M <= 16): fp32 K-slice slabs [ks, 16, RT]",
+        py::arg("x"), py::arg("a_img"), py::arg("ids"), py::arg("ks") = 0, py::arg("out") = py::none());
+  m.def("gemv16_rows_lora", &gemv16_rows_lora, "16-row decode GEMV with per-row LoRA adapters in its tail",
+        py::arg("fmt"), py::arg("a"), py::arg("w"), py::arg("aux"), py::arg("act"), py::arg("residual"),
+        py::arg("norm_eps"), py::arg("t"), py::arg("b_img"), py::arg("ids"), py::arg("seg1"), py::arg("seg2"),
+        py::arg("out") = py::none());
   m.def("get_tuning", &get_tuning, "the launchers' kernel-selection knobs (rt::Tuning) as a dict");
   m.def("set_tuning", &set_tuning, "update rt::Tuning fields from a dict (unknown keys raise)");
   m.def("attn_decode_fused", &attn_decode_fused, "RoPE + KV append + split-K decode attention + combine",

@@ -460,15 +460,70 @@ struct ImgFp4 {
   }
 };
 
+// Per-row LoRA adapters of the 16-row kernel (docs/DESIGN.md "Per-request adapters"): row b adds
+//   rs_b * sum_{j < R} T[b][seg(n) R + j] * Bimg[ids[b]][n][j]
+// to output column n before bias / activation / the SwiGLU pair; ids[b] < 0 = no adapter (the row
+// takes exactly the arithmetic of the kernel without this term). T = lora_rows_shrink_kernel's
+// fp32 K-slice slabs [ks][16][ldt], summed here in slice order; Bimg [slots][N][R] bf16 holds, per
+// weight row, the R entries of its own sub-projection seg(n) = (n >= seg1) + (n >= seg2) (q|k|v;
+// SwiGLU: gate rows segment 0, up rows segment 1).
+struct LoraRows {
+  const float* T;
+  const bf16_t* Bimg;
+  const int* ids;
+  int R, ldt, ks, seg1, seg2, slots;  // ids outside [0, slots) count as no adapter
+};
+__device__ __forceinline__ const LoraRows& lora_rows_of(const LoraRows& lr) { return lr; }
+
+// the adapter term of (row, weight row n) of adapter a, rank entries in index order
+__device__ __forceinline__ float lora_rows_delta(const LoraRows& lr, int N, int row, int a, int n, int seg) {
+  const bf16_t* b = lr.Bimg + ((long)a * N + n) * lr.R;
+  const float* t = lr.T + (long)row * lr.ldt + seg * lr.R;
+  float d = 0.f;
+  for (int j0 = 0; j0 < lr.R; j0 += 8) {
+    float tj[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, f[8];
+    for (int s = 0; s < lr.ks; ++s) {
+      const float4 lo = *(const float4*)(t + (long)s * 16 * lr.ldt + j0);
+      const float4 hi = *(const float4*)(t + (long)s * 16 * lr.ldt + j0 + 4);
+      tj[0] += lo.x; tj[1] += lo.y; tj[2] += lo.z; tj[3] += lo.w;
+      tj[4] += hi.x; tj[5] += hi.y; tj[6] += hi.z; tj[7] += hi.w;
+    }
+    unpack8(*(const uint4*)(b + j0), f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) d = fmaf(tj[e], f[e], d);
+  }
+  return d;
+}
+
 // Tail of the 16-row kernel: the waves' partial sums meet in LDS and are summed in wave order, then
-// in-GEMM RMS-norm scaling, per-column scale (Fmt::COL_SCALE), bias, activation or the SwiGLU
-// gate / up pair, residual, bf16 / fp32 store.
-template <class Fmt, bool OUT_F32, bool PAIR, int NW>
+// in-GEMM RMS-norm scaling, per-column scale (Fmt::COL_SCALE), the per-row adapter term (LR = one
+// LoraRows; the empty pack is the plain kernel), bias, activation or the SwiGLU gate / up pair,
+// residual, bf16 / fp32 store.
+template <class Fmt, bool OUT_F32, bool PAIR, int NW, class... LR>
 __device__ __forceinline__ void gemv16_finish(const GemmArgs& p, const f32x4& acc, const f32x4& accu, float sq,
-                                              float (&red)[NW][16][PAIR ? 33 : 17], float (&rsq)[NW][16], int grp) {
+                                              float (&red)[NW][16][PAIR ? 33 : 17], float (&rsq)[NW][16], int grp,
+                                              const LR&... lrs) {
+  constexpr bool LORA = sizeof...(LR) == 1;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int frow = lane & 15, g = lane >> 4;
   const bool normed = p.norm_eps > 0.f;
+  // adapter term of this thread's (row, column): read before the barrier, T and Bimg are L2 hits
+  float dl = 0.f, dlu = 0.f;
+  bool adapted = false;
+  if constexpr (LORA) {
+    const LoraRows& lr = lora_rows_of(lrs...);
+    const int lrow = tid >> 4, lcol = grp * 16 + (tid & 15);
+    const int a = lrow < p.M ? lr.ids[lrow] : -1;
+    adapted = a >= 0 && a < lr.slots;
+    if (adapted) {
+      if constexpr (PAIR) {
+        dl = lora_rows_delta(lr, p.N, lrow, a, lcol, 0);
+        dlu = lora_rows_delta(lr, p.N, lrow, a, p.N / 2 + lcol, 1);
+      } else {
+        dl = lora_rows_delta(lr, p.N, lrow, a, lcol, (lcol >= lr.seg1) + (lcol >= lr.seg2));
+      }
+    }
+  }
   // acc[r] of lane (frow, g) = C[row 4 g + r][16 grp + frow] over this wave's k range; the X row
   // sum of squares of row frow is spread over its 4 g lanes
 #pragma unroll
@@ -500,10 +555,16 @@ __device__ __forceinline__ void gemv16_finish(const GemmArgs& p, const f32x4& ac
       const int F = p.N / 2;
       float up = uu * rs;
       if constexpr (Fmt::COL_SCALE) { y *= p.sb[col]; up *= p.sb[F + col]; }
+      if constexpr (LORA) {
+        if (adapted) { y += rs * dl; up += rs * dlu; }
+      }
       if (p.bias) { y += bf2f(p.bias[col]); up += bf2f(p.bias[F + col]); }
       y = y / (1.f + __expf(-y)) * up;
     } else {
       if constexpr (Fmt::COL_SCALE) y *= p.sb[col];
+      if constexpr (LORA) {
+        if (adapted) y += rs * dl;
+      }
       if (p.bias) y += bf2f(p.bias[col]);
       y = apply_act(y, p.act);
       if (p.R) y += bf2f(p.R[(long)row * p.ldr + col]);
@@ -513,9 +574,13 @@ __device__ __forceinline__ void gemv16_finish(const GemmArgs& p, const f32x4& ac
   }
 }
 
-// simg: the scale image (Fmt::SCALED), else unused
-template <class Fmt, bool OUT_F32, int DEPTH, bool PAIR, int NW>
-__global__ __launch_bounds__(64 * NW) void gemv16_kernel(GemmArgs p, const unsigned short* __restrict__ simg) {
+// simg: the scale image (Fmt::SCALED), else unused. LR: empty, or one LoraRows = the per-row adapter
+// operands as a third kernel argument. A trailing pack keeps ONE kernel body and leaves the plain
+// forms (empty pack) exactly the code, registers and LDS they had before the adapter form existed: a
+// body shared through an inlined device function changed the register allocation and schedule of the
+// bf16 forms (docs/DESIGN.md "Per-request adapters").
+template <class Fmt, bool OUT_F32, int DEPTH, bool PAIR, int NW, class... LR>
+__global__ __launch_bounds__(64 * NW) void gemv16_kernel(GemmArgs p, const unsigned short* __restrict__ simg, LR... lr) {
   // M <= 16 rows of X: the MFMA's 16 A rows (row frow of lane (frow, g); rows >= M repeat M - 1)
   // NW waves split the group's K chunks (NW = 8: twice the weight bytes in flight per workgroup)
   __shared__ float red[NW][16][PAIR ? 33 : 17];
@@ -594,7 +659,49 @@ __global__ __launch_bounds__(64 * NW) void gemv16_kernel(GemmArgs p, const unsig
 #pragma unroll
   for (int i = 0; i < DEPTH - 1; ++i)
     if (c + i < c_end) mma(r[i]);
-  gemv16_finish<Fmt, OUT_F32, PAIR, NW>(p, acc, accu, sq, red, rsq, grp);
+  gemv16_finish<Fmt, OUT_F32, PAIR, NW>(p, acc, accu, sq, red, rsq, grp, lr...);
+}
+
+// Shrink of the per-row adapters: T[z][b][rg 16 + i] = sum over K slice z of Aimg[slot][rg 16 + i][k]
+// x[b][k] for the rows b with ids[b] == slot. Grid (rank group of 16, slot, K slice): a workgroup
+// reads its slot's 16 Aimg rows once for all rows of X (the MFMA's 16 A rows; rows >= M repeat
+// M - 1) and exits on a uniform branch when no row uses the slot. Its 4 waves split the slice's
+// 64-k chunks, meet in LDS and are summed in wave order; the K slices stay separate fp32 slabs that
+// the expand (lora_rows_delta) sums in slice order: no atomics, one fixed association per shape.
+// Rows of other slots, base rows and ranks >= RT are not written (and never read).
+__global__ __launch_bounds__(256) void lora_rows_shrink_kernel(const bf16_t* __restrict__ X, long ldx,
+                                                               const bf16_t* __restrict__ Aimg, const int* __restrict__ ids,
+                                                               float* __restrict__ T, int M, int K, int RT) {
+  __shared__ float red[4][16][17];
+  const int slot = blockIdx.y, rg = blockIdx.x, z = blockIdx.z, ks = gridDim.z;
+  bool used = false;
+  for (int b = 0; b < M; ++b) used |= ids[b] == slot;
+  if (!used) return;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int frow = lane & 15, g = lane >> 4;
+  const int nc = K / 64;
+  const int z0 = z * nc / ks, z1 = (z + 1) * nc / ks;
+  const int c0 = z0 + wid * (z1 - z0) / 4, c1 = z0 + (wid + 1) * (z1 - z0) / 4;
+  const bf16_t* xrow = X + (long)min(frow, M - 1) * ldx + g * 8;
+  const bf16_t* arow = Aimg + ((long)slot * RT + min(rg * 16 + frow, RT - 1)) * K + g * 8;
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int c = c0; c < c1; ++c) {
+    const uint4 x0 = *(const uint4*)(xrow + c * 64), x1 = *(const uint4*)(xrow + c * 64 + 32);
+    const uint4 a0 = *(const uint4*)(arow + c * 64), a1 = *(const uint4*)(arow + c * 64 + 32);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, x0), __builtin_bit_cast(bf16x8, a0), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, x1), __builtin_bit_cast(bf16x8, a1), acc, 0, 0, 0);
+  }
+  // acc[r] of lane (frow, g) = T[row 4 g + r][rank rg 16 + frow] over this wave's chunks
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) red[wid][4 * g + rr][frow] = acc[rr];
+  __syncthreads();
+  const int row = tid >> 4, rank = rg * 16 + (tid & 15);
+  if (row < M && rank < RT && ids[row] == slot) {
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) t += red[w][row][tid & 15];
+    T[((long)z * 16 + row) * RT + rank] = t;
+  }
 }
 
 // Shared tail of the M <= 64 kernels: split-K hand-off (write-through slabs + ticket, last arriver
@@ -1524,6 +1631,65 @@ extern "C" int rt_gemv_fp4(const void* A, long lda, const void* img, const void*
   const bool pair = act == ACT_SWIGLU;
   if (M > 16 || K <= 0 || K % 256 || N % 16 || (pair && N % 64) || lda % 8) return -4;
   launch_gemv16<ImgFp4>(p, (const unsigned short*)simg, out_f32, pair, 3, gemv16_auto_waves(N / 16), stream);
+  RT_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Per-row LoRA adapters at M <= 16: the shrink launch and the 16-row kernel with the adapter tail
+// ---------------------------------------------------------------------------------------------
+// K slices of the shrink: one per 2048 k, at most 8 (a function of K alone, so a row's T does not
+// depend on the batch it sits in); `ks` > 0 forces a count (tests).
+extern "C" int rt_lora_rows_slices(int K) { return std::max(1, std::min(8, K / 2048)); }
+
+// T [ks][16][RT] fp32 (RT = nseg R) from X [M <= 16, K] and Aimg [slots][RT][K]
+extern "C" int rt_lora_rows_shrink(const void* X, long ldx, const void* Aimg, const int* ids, float* T, int M, int K, int RT,
+                                   int slots, int ks, hipStream_t stream) {
+  if (M <= 0) return 0;
+  if (M > 16 || K <= 0 || K % 64 || RT <= 0 || RT % 8 || slots <= 0 || ks <= 0 || ks > 64 || (M > 1 && ldx % 8)) return -4;
+  hipLaunchKernelGGL(lora_rows_shrink_kernel, dim3((RT + 15) / 16, slots, ks), dim3(256), 0, stream, (const bf16_t*)X, ldx,
+                     (const bf16_t*)Aimg, ids, T, M, K, RT);
+  RT_LAUNCH_CHECK();
+  return 0;
+}
+
+// The built adapter forms follow the default form of each image (launch_gemv16): bf16 depth 4 at 4 /
+// 8 waves, fp8 depth 4 at 4 waves, MXFP4 depth 3 at 4 / 8 waves; the SwiGLU pair at 4 waves.
+template <class Fmt, int DEPTH>
+static void launch_gemv16_rows_lora(const GemmArgs& p, const unsigned short* simg, const LoraRows& lr, bool pair, int nw,
+                                    hipStream_t stream) {
+  const dim3 grid(pair ? p.N / 32 : p.N / 16);
+#define GEMV16L(P, W) \
+  hipLaunchKernelGGL((gemv16_kernel<Fmt, false, DEPTH, P, W, LoraRows>), grid, dim3(64 * W), 0, stream, p, simg, lr)
+  if (pair) GEMV16L(true, 4);
+  else if (nw == 8 && !std::is_same_v<Fmt, ImgFp8>) GEMV16L(false, 8);
+  else GEMV16L(false, 4);
+#undef GEMV16L
+}
+
+// C[M, N] (bf16) = epilogue(rstd(X) (X W'^T [* sb] + T Bimg[ids]^T)), M <= 16, W' one of the three
+// 16-row images: fmt 0 bf16 tile-ordered, 1 fp8 (sb = per-column scales), 2 MXFP4 (simg = scale
+// image). Always the 16-row kernel, in the wave count the image's plain launch uses at this shape.
+extern "C" int rt_gemv16_rows_lora(int fmt, const void* A, long lda, const void* img, const void* simg, const float* sb,
+                                   void* C, long ldc, int M, int N, int K, int act, const void* R, long ldr,
+                                   float norm_eps, const float* T, const void* Bimg, const int* ids, int rank, int nseg,
+                                   int ks, int seg1, int seg2, int slots, hipStream_t stream) {
+  GemmArgs p = skinny_args(A, lda, img, 0, nullptr, C, ldc, M, N, K, act, R, ldr, norm_eps, 1);
+  p.sb = sb;
+  if (M <= 0 || N <= 0) return 0;
+  const bool pair = act == ACT_SWIGLU;
+  const int S = fmt == 0 ? 1 : fmt == 1 ? 2 : 4;
+  if (fmt < 0 || fmt > 2 || M > 16 || K <= 0 || K % (64 * S) || N % 16 || (pair && N % 64) || (M > 1 && lda % 8)) return -4;
+  if ((rank != 8 && rank != 16 && rank != 32 && rank != 64) || nseg < 1 || nseg > 3 || nseg * rank > 192 || ks <= 0 ||
+      (pair && nseg != 2) || (fmt == 1 && !sb) || (fmt == 2 && !simg))
+    return -4;
+  const LoraRows lr{T, (const bf16_t*)Bimg, ids, rank, nseg * rank, ks, seg1, seg2, slots};
+  if (fmt == 0)
+    launch_gemv16_rows_lora<ImgBf16, 4>(p, nullptr, lr, pair, gemv16_auto_waves(pair ? N / 32 : N / 16), stream);
+  else if (fmt == 1)
+    launch_gemv16_rows_lora<ImgFp8, 4>(p, nullptr, lr, pair, 4, stream);
+  else
+    launch_gemv16_rows_lora<ImgFp4, 3>(p, (const unsigned short*)simg, lr, pair, gemv16_auto_waves(N / 16), stream);
   RT_LAUNCH_CHECK();
   return 0;
 }

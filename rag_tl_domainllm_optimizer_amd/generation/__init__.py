@@ -252,6 +252,10 @@ class Generator:
         # allocated on first use; _rows_on selects the per-row sampler and bookkeeping in _emit
         self.rowp = None
         self._rows_on = False
+        # per-request adapters (ContinuousBatcher(adapters=bank)): the bank and a static adapter slot
+        # per row (-1 = base model), written at admission outside any graph like the row parameters
+        self.adapters = None
+        self.adapter_ids = None
 
     # ------------------------------------------------------------------ one decode step (device only)
     def _bucket(self, B: int) -> int:
@@ -268,8 +272,13 @@ class Generator:
         # (decode_update on the GPU, _update_cpu on the CPU) — no elementwise launches here
         nb = self._nb
         cache = self.cache if nb == self.max_batch else _SubCache(self.cache, nb)
-        h = self.model.decode(self.tok_in[:nb], self.pos[:nb], self.kv_len[:nb], self.attn_len[:nb],
-                              self.kv_start[:nb], cache, self.workspace)
+        if self.adapters is not None:
+            h = self.model.decode(self.tok_in[:nb], self.pos[:nb], self.kv_len[:nb], self.attn_len[:nb],
+                                  self.kv_start[:nb], cache, self.workspace,
+                                  adapters=(self.adapters, self.adapter_ids[:nb]))
+        else:
+            h = self.model.decode(self.tok_in[:nb], self.pos[:nb], self.kv_len[:nb], self.attn_len[:nb],
+                                  self.kv_start[:nb], cache, self.workspace)
         self._emit(h, params, eos_ids, pad_id)
 
     def _lookup_buffers(self, K: int) -> "_LookupState":
@@ -530,6 +539,8 @@ class Generator:
             key = (T, "rows", tuple(eos_list), pad_id, self._nb)
         if _fp4_decode_on(self.model):
             key = key + ("fp4",)  # the captured step of the other setting streams other weight images
+        if self.adapters is not None:
+            key = key + ("adapters",)  # slots are read from the row buffer: one graph per bucket whatever the mix
         if self._lk is not None:
             # a verify step is its own graph per (K, n-gram length); plain keys are unchanged
             key = key + ("lookup", params.lookup_tokens, params.lookup_ngram)
@@ -738,6 +749,29 @@ class _RowCache:
         return (self.ks[layer], self.vs[layer]) if self.fp8 else (None, None)
 
 
+def _check_bank(gen: "Generator", params: SamplingParams, bank):
+    """Per-request adapters run decode steps of at most 16 rows on the fused Llama / Mistral layer
+    over the unmerged base; everything else is refused with the reason."""
+    model = gen.model
+    if gen.max_batch > 16:
+        raise ValueError(f"per-request adapters: max_batch {gen.max_batch} exceeds the 16 rows of the per-row adapter "
+                         f"kernels")
+    if params.lookup_tokens > 0:
+        raise ValueError("per-request adapters: prompt-lookup decoding (lookup_tokens > 0) is not supported")
+    if gen.cfg.arch == "opt":
+        raise ValueError("per-request adapters: learned-position (opt) models have no fused decode layer")
+    if bank.model is not model:
+        raise ValueError("per-request adapters: the bank was built for another model")
+    if any(layer.lora and layer.lora_enabled for layer in model.layers):
+        raise ValueError("per-request adapters: the model carries LoRA adapters of its own, which decode merged into "
+                         "the base weights; save them (save_adapter) and load them into the bank instead")
+    if any(getattr(layer, "fp8_enabled", False) for layer in model.layers):
+        raise ValueError("per-request adapters: fp8 weights (set_fp8) are not supported yet: the fp8 prefill merges "
+                         "adapters into the weights")
+    if not getattr(model, "fused_decode", True):
+        raise ValueError("per-request adapters need the fused decode layer (model.fused_decode)")
+
+
 @dataclass
 class FinishedRow:
     tag: object
@@ -746,6 +780,7 @@ class FinishedRow:
     prompt_len: int
     steps_waited: int
     seed: Optional[int] = None  # per-request sampling: the seed the row drew with (given or derived)
+    adapter: Optional[str] = None  # per-request adapters: the adapter the row ran with (None: base model)
 
 
 class ContinuousBatcher:
@@ -772,7 +807,9 @@ class ContinuousBatcher:
     rows that finished (a host read of the per-row flags once per call)."""
 
     def __init__(self, gen: Generator, params: SamplingParams, pad_id: int = 0, eos_ids: Sequence[int] = (),
-                 per_request: bool = False):
+                 per_request: bool = False, adapters=None):
+        if adapters is not None:
+            _check_bank(gen, params, adapters)
         if params.lookup_tokens > 0:
             raise NotImplementedError("prompt-lookup decoding is not supported with continuous batching")
         if _fp4_decode_on(gen.model) and gen.max_batch > 16:
@@ -805,6 +842,14 @@ class ContinuousBatcher:
             # every row starts at the batcher's defaults (the capture below runs the step on them)
             g._row_buffers().write(0, [RequestSampling().resolve(params, T, 0)] * MB)
         self._prev_merged = g.model.set_lora_merged(g.merge_lora) if hasattr(g.model, "set_lora_merged") else None
+        self.adapters = adapters
+        self.row_adapter = {}  # row -> adapter name
+        g.adapters = adapters
+        if adapters is not None:
+            if g.adapter_ids is None:
+                g.adapter_ids = torch.empty(MB, dtype=torch.int32, device=dev)
+            g.adapter_ids.fill_(-1)
+            adapters.refresh()
         if hasattr(g.model, "refresh_decode_weights"):
             g.model.refresh_decode_weights(MB)
         if T > 1:
@@ -815,6 +860,7 @@ class ContinuousBatcher:
 
     def close(self):
         self.gen._rows_on = False
+        self.gen.adapters = None
         if self._prev_merged is not None:
             self.gen.model.set_lora_merged(self._prev_merged)
             self._prev_merged = None
@@ -826,19 +872,28 @@ class ContinuousBatcher:
         return len(self.rows)
 
     @torch.no_grad()
-    def admit(self, prompt: List[int], tag=None, sampling: Optional[RequestSampling] = None) -> int:
-        return self.admit_many([prompt], [tag], [sampling])[0]
+    def admit(self, prompt: List[int], tag=None, sampling: Optional[RequestSampling] = None,
+              adapter: Optional[str] = None) -> int:
+        return self.admit_many([prompt], [tag], [sampling], [adapter])[0]
 
     @torch.no_grad()
-    def admit_many(self, prompts: List[List[int]], tags=None, sampling=None) -> List[int]:
+    def admit_many(self, prompts: List[List[int]], tags=None, sampling=None, adapters=None) -> List[int]:
         """Admit len(prompts) <= free_rows() requests. The lowest free rows are taken and every run
         of consecutive rows is prefilled as ONE left-padded batch into its cache rows.
-        ``sampling``: one ``RequestSampling`` or None per prompt (``per_request`` batchers only)."""
+        ``sampling``: one ``RequestSampling`` or None per prompt (``per_request`` batchers only).
+        ``adapters``: one loaded adapter name or None (base model) per prompt (batchers with a bank)."""
         g = self.gen
         tags = list(tags) if tags is not None else [None] * len(prompts)
         sampling = list(sampling) if sampling is not None else [None] * len(prompts)
+        adapters = list(adapters) if adapters is not None else [None] * len(prompts)
         if len(sampling) != len(prompts):
             raise ValueError(f"{len(sampling)} sampling entries for {len(prompts)} prompts")
+        if len(adapters) != len(prompts):
+            raise ValueError(f"{len(adapters)} adapter entries for {len(prompts)} prompts")
+        if self.adapters is None and any(a is not None for a in adapters):
+            raise ValueError("per-request adapters need ContinuousBatcher(adapters=bank)")
+        # unknown names fail here (KeyError), before any row is taken
+        slots = [self.adapters.slot(a) for a in adapters] if self.adapters is not None else None
         if not self.per_request and any(s is not None for s in sampling):
             raise ValueError("per-request sampling settings need ContinuousBatcher(per_request=True)")
         if len(prompts) > len(self.free):
@@ -855,18 +910,39 @@ class ContinuousBatcher:
         self.free.sort()
         rows, self.free = self.free[:len(prompts)], self.free[len(prompts):]
         try:
-            self._admit_runs(rows, prompts, tags, resolved)
+            if slots is None:
+                self._admit_runs(rows, prompts, tags, resolved)
+            else:
+                self._admit_adapter_runs(rows, prompts, tags, resolved, adapters, slots)
         except BaseException:
             # all-or-nothing: rows of this call that were already prefilled leave the batch again
             # (inactive, back on the free list), so the caller can fail every request it passed
             for b in rows:
                 self.rows.pop(b, None)
                 self.row_seed.pop(b, None)
+                self.row_adapter.pop(b, None)
             g.active[torch.tensor(rows, device=g.device)] = 0
             self.free = sorted(self.free + rows)
             raise
         self.admitted += len(prompts)
         return rows
+
+    def _admit_adapter_runs(self, rows, prompts, tags, resolved, names, slots):
+        """``_admit_runs`` per piece of consecutive rows with one adapter: each piece is prefilled with
+        its slot active, unmerged (``AdapterBank.active``), under ``ops.batch_invariant`` — the
+        K-extension GEMMs whatever the piece's token count, i.e. the scoring forward's numerics."""
+        g = self.gen
+        i = 0
+        while i < len(rows):
+            j = i + 1
+            while j < len(rows) and rows[j] == rows[j - 1] + 1 and slots[j] == slots[i]:
+                j += 1
+            g.adapter_ids[rows[i]:rows[i] + (j - i)].fill_(slots[i])
+            with self.adapters.active(names[i]), ops.batch_invariant():
+                self._admit_runs(rows[i:j], prompts[i:j], tags[i:j], None if resolved is None else resolved[i:j])
+            for r in range(i, j):
+                self.row_adapter[rows[r]] = names[r]
+            i = j
 
     def _admit_runs(self, rows, prompts, tags, resolved=None):
         g = self.gen
@@ -927,6 +1003,6 @@ class ContinuousBatcher:
             for b, n, t, lp in zip(done, lens, toks, lps):
                 tag, S, s0 = self.rows.pop(b)
                 out.append(FinishedRow(tag, t[:n].tolist(), lp[:n].tolist(), S, self.steps - s0,
-                                       self.row_seed.pop(b, None)))
+                                       self.row_seed.pop(b, None), self.row_adapter.pop(b, None)))
                 self.free.append(b)
         return out

@@ -141,10 +141,44 @@ class DecoderLayer(nn.Module):
                 if c is not None:
                     c.image(w) if ops.on_gpu(w) else c.get(w)
 
-    def decode_fused(self, h, attend):
+    def _dec_rows(self, f8name: str, name: str, w: torch.Tensor, m: int, act: int = 0):
+        """``_dec`` for a step with per-row adapters: always an image of the 16-row kernel (MXFP4,
+        fp8, else the tile-ordered bf16 one whatever ``shuffle_enabled`` says)."""
+        if not ops.on_gpu(w):  # the eager twin: only the MXFP4 image changes the numbers
+            f4 = self._f4(name, w, m, act)
+            return {"fp4": f4} if f4 is not None else {}
+        kw = self._dec(f8name, name, w, m, act)
+        if kw.get("fp4") is None and kw.get("fp8") is None:
+            kw["shuf"] = self._shufc.setdefault(name, ops.ShufCache())
+        return kw
+
+    def _decode_fused_rows(self, h, attend, bank_layer, ids):
+        """``decode_fused`` with per-row adapters (models.lora.AdapterBank, at most 16 rows): the base
+        weights stay unmerged; every projection runs one shrink launch (fp32 rank-space T) and the
+        16-row kernel with the adapter term in its tail. Rows with ids < 0 are the base model."""
+        eps = self.cfg.norm_eps
+        m = h.shape[0]
+
+        def proj(x, w, grp, f8name, **kw):
+            e = bank_layer[grp]
+            t = ops.lora_rows_shrink(x, e["a_img"], ids)
+            return ops.gemm_decode(x, w, rows_lora=(t, e["b_img"], ids, e["segs"]), **kw,
+                                   **self._dec_rows(f8name, grp, w, m, kw.get("act", 0)))
+
+        wq = self._fold.setdefault("qkv", ops.FoldCache()).get(self.qkv_w, self.ln1_w)
+        qkv = proj(h, wq, "qkv", "qkv_folded", norm_eps=eps)
+        h = proj(attend(qkv), self.o_w, "o", "o", residual=h)
+        wgu = self._fold.setdefault("gate_up", ops.FoldCache()).get(self.gate_up_w, self.ln2_w)
+        f = proj(h, wgu, "gate_up", "gate_up_folded", act=ops.ACT_SWIGLU, norm_eps=eps)
+        return proj(f, self.down_w, "down", "down", residual=h)
+
+    def decode_fused(self, h, attend, rows=None):
         """One Llama/Mistral layer of a decode step in four kernels: [RMSNorm folded into the qkv
         GEMM] -> attention (RoPE + append + split-K) -> [o GEMM + residual] -> [RMSNorm folded into
-        the gate/up GEMM + SwiGLU] -> [down GEMM + residual]. ``h`` is the bf16 residual stream."""
+        the gate/up GEMM + SwiGLU] -> [down GEMM + residual]. ``h`` is the bf16 residual stream.
+        ``rows`` = (the AdapterBank's images of this layer, adapter slot per row): per-row adapters."""
+        if rows is not None:
+            return self._decode_fused_rows(h, attend, *rows)
         cfg = self.cfg
         eps = cfg.norm_eps
         m = h.shape[0]
@@ -412,17 +446,21 @@ class CausalLM(nn.Module):
         return self.final_norm(x, residual)
 
     @torch.no_grad()
-    def decode(self, tokens, pos, slot, attn_len, kv_start, cache, workspace=None) -> torch.Tensor:
+    def decode(self, tokens, pos, slot, attn_len, kv_start, cache, workspace=None, adapters=None) -> torch.Tensor:
         """One step: tokens [B] at rotary position pos [B] written to cache slot ``slot`` [B];
-        attention over ``attn_len`` [B] keys. Returns final hidden [B, H]."""
+        attention over ``attn_len`` [B] keys. Returns final hidden [B, H]. ``adapters`` = (AdapterBank,
+        int32 slot per row, < 0 = base model): per-row adapters on the fused layer, B <= 16."""
         cfg = self.cfg
+        if adapters is not None and (tokens.shape[0] > 16 or cfg.arch == "opt" or not self.fused_decode
+                                     or torch.is_grad_enabled()):
+            raise ValueError("decode: per-row adapters need the fused decode layer at no more than 16 rows")
         cos, sin = self.rope(tokens.device)
         x = self.embed_tokens(tokens, pos)
         fp8 = bool(self.layers) and self.layers[0].fp8_enabled
         max_b = self.fused_decode_max_batch_fp8 if fp8 else self.fused_decode_max_batch
         fp4 = bool(self.layers) and self.layers[0].fp4_decode  # its CPU twin runs the fused layer too
-        if (self.fused_decode and cfg.arch != "opt" and (x.is_cuda or fp4) and x.shape[0] <= max_b
-                and not torch.is_grad_enabled()):
+        if adapters is not None or (self.fused_decode and cfg.arch != "opt" and (x.is_cuda or fp4) and x.shape[0] <= max_b
+                                    and not torch.is_grad_enabled()):
             h = x
             kv8 = getattr(cache, "fp8", False)
             for li, layer in enumerate(self.layers):
@@ -431,7 +469,7 @@ class CausalLM(nn.Module):
                     return ops.decode_step_attention(qkv, cache.k[li], cache.v[li], slot, attn_len, cfg.num_heads,
                                                      pos, cos, sin, kv_start, cfg.sliding_window,
                                                      workspace=workspace, k_scale=ks, v_scale=vs)
-                h = layer.decode_fused(h, attend)
+                h = layer.decode_fused(h, attend, rows=None if adapters is None else (adapters[0].layer(li), adapters[1]))
             y, _ = ops.rms_norm(h, self.norm_w, cfg.norm_eps)
             return y
         residual = None

@@ -7,6 +7,7 @@ reference README declares (README.md:15,29) but does not implement.
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import math
 import os
@@ -205,3 +206,202 @@ def _group_weight(layer, cfg, grp):
     return {"qkv": layer.qkv_w, "o": layer.o_w, "gate_up": getattr(layer, "gate_up_w", None),
             "down": getattr(layer, "down_w", None), "fc1": getattr(layer, "fc1_w", None),
             "fc2": getattr(layer, "fc2_w", None)}[grp]
+
+
+# ------------------------------------------------------------------------------------------------
+# Per-request adapters: several adapters resident over one frozen base (docs/DESIGN.md "Per-request
+# adapters")
+_BANK_GROUPS = (("qkv", ("q_proj", "k_proj", "v_proj"), "ln1_w"), ("o", ("o_proj",), None),
+                ("gate_up", ("gate_proj", "up_proj"), "ln2_w"), ("down", ("down_proj",), None))
+
+
+class AdapterBank:
+    """``slots`` LoRA adapters of rank <= ``r_max`` resident over one frozen Llama / Mistral base, for
+    decode steps whose rows each pick their own adapter (``ContinuousBatcher(adapters=bank)``).
+
+    Per layer and fused projection (qkv, o, gate_up, down) the bank holds, for all slots at fixed
+    addresses (``load`` / ``unload`` write in place, so captured decode steps stay valid):
+      * ``a_img`` [slots, nseg R, K] bf16: ``s A`` of every sub-projection, times the RMSNorm weight
+        where the decode step folds it into the base weight (qkv, gate_up), rounded to bf16 once;
+      * ``b_img`` [slots, N, R] bf16: per output column the R entries of its own sub-projection;
+      * for the folded projections ``a_raw`` (``s A`` without the norm weight) for the token-parallel
+        path, which applies the norm as its own kernel.
+    Ranks below R are zero-padded, a target module an adapter lacks is zeros. The token-parallel
+    path (prefill, scoring) runs ONE slot through the K-extension GEMMs: :meth:`active` points
+    every projection's ``ops.LoRAGroup`` compute images at that slot, unmerged."""
+
+    def __init__(self, model, slots: int = 8, r_max: int = 16):
+        cfg = model.cfg
+        if cfg.arch == "opt":
+            raise ValueError("AdapterBank: learned-position (opt) models have no fused decode layer")
+        if r_max not in (8, 16, 32, 64):
+            raise ValueError(f"AdapterBank: r_max must be 8, 16, 32 or 64, got {r_max}")
+        if slots < 1:
+            raise ValueError("AdapterBank: at least one slot")
+        self.model, self.cfg, self.slots, self.R = model, cfg, int(slots), int(r_max)
+        self.names: List[Optional[str]] = [None] * self.slots
+        self.version = [0] * self.slots
+        dev, dt = model.embed.device, model.dtype
+        R = self.R
+        self.layers = []   # per layer: group -> dict(a_img, b_img, a_raw, segs, scratch LoRAGroup)
+        self._master = {}  # slot -> {(layer, group): fp32 s A on the CPU} of the folded projections
+        self._fold_key = {}
+        for layer in model.layers:
+            ent = {}
+            for grp, projs, _ in _BANK_GROUPS:
+                K = _proj_in(cfg, projs[0])
+                N = _group_out(cfg, grp)
+                nseg = len(projs)
+                a_img = torch.zeros(self.slots, nseg * R, K, dtype=dt, device=dev)
+                folded = grp in ("qkv", "gate_up")
+                rp = max(64, (nseg * R + 63) // 64 * 64)
+                # the one-slot K-extension images of the token-parallel path; the off-diagonal blocks
+                # and the padding of ub / a_pad stay zero, a slot switch copies the diagonal blocks
+                g = ops.LoRAGroup(list(projs), [], [], [_proj_rows(cfg, p)[0] for p in projs], [1.0] * nseg, N)
+                g.a_pad = torch.zeros(rp, K, dtype=dt, device=dev)
+                g.ub = torch.zeros(N, rp, dtype=dt, device=dev)
+                ent[grp] = dict(a_img=a_img, b_img=torch.zeros(self.slots, N, R, dtype=dt, device=dev),
+                                a_raw=torch.zeros_like(a_img) if folded else a_img,
+                                segs=tuple(_proj_rows(cfg, p)[0] for p in projs[1:]), group=g)
+            self.layers.append(ent)
+        self._pf_slot = None  # (slot, version) the one-slot images hold
+
+    # -------------------------------------------------------------- slots
+    def loaded(self) -> List[str]:
+        return [n for n in self.names if n is not None]
+
+    def slot(self, name: Optional[str]) -> int:
+        """Slot of a loaded adapter; -1 for None (the base model)."""
+        if name is None:
+            return -1
+        if name not in self.names:
+            raise KeyError(f"adapter {name!r} is not loaded (loaded: {self.loaded()})")
+        return self.names.index(name)
+
+    def layer(self, li: int):
+        return self.layers[li]
+
+    @torch.no_grad()
+    def load(self, name: str, peft_dir: str) -> int:
+        """Read a PEFT adapter directory (``save_adapter``'s layout) into ``name``'s slot — a free one,
+        or in place over the adapter of that name. Everything is validated before a byte is written."""
+        from safetensors.torch import load_file
+
+        if not isinstance(name, str) or not name:
+            raise ValueError("AdapterBank.load: the adapter name must be a non-empty string")
+        with open(os.path.join(peft_dir, "adapter_config.json")) as f:
+            d = json.load(f)
+        lc = LoraConfig(**{k: v for k, v in d.items() if k in LoraConfig.__dataclass_fields__})
+        if lc.r > self.R:
+            raise ValueError(f"adapter {name!r}: rank {lc.r} exceeds the bank's r_max {self.R}")
+        sd = load_file(os.path.join(peft_dir, "adapter_model.safetensors"))
+        cfg, R, s = self.cfg, self.R, float(lc.scaling)
+        staged, used = [], set()
+        for li in range(len(self.layers)):
+            for grp, projs, _ in _BANK_GROUPS:
+                K, N = _proj_in(cfg, projs[0]), _group_out(cfg, grp)
+                a = torch.zeros(len(projs) * R, K)
+                b = torch.zeros(N, R)
+                for i, proj in enumerate(projs):
+                    base = f"{_layer_prefix(cfg, li)}.{_module_path(cfg, proj)}"
+                    ka, kb = f"{base}.lora_A.weight", f"{base}.lora_B.weight"
+                    if ka not in sd and kb not in sd:
+                        continue  # a target module this adapter lacks: zeros
+                    if ka not in sd or kb not in sd:
+                        raise ValueError(f"adapter {name!r}: {base} has only one of lora_A / lora_B")
+                    row0, n = _proj_rows(cfg, proj)
+                    A, B = sd[ka].float(), sd[kb].float()
+                    if A.dim() != 2 or B.dim() != 2 or A.shape[1] != K or B.shape[0] != n or A.shape[0] != B.shape[1] \
+                            or A.shape[0] > R:
+                        raise ValueError(f"adapter {name!r}: {base} has A {tuple(A.shape)}, B {tuple(B.shape)}; the base "
+                                         f"model needs A [r <= {R}, {K}], B [{n}, r]")
+                    r = A.shape[0]
+                    a[i * R:i * R + r] = A * s
+                    b[row0:row0 + n, :r] = B
+                    used.update((ka, kb))
+                staged.append((li, grp, a, b))
+        extra = [k for k in sd if k not in used]
+        if extra:
+            raise ValueError(f"adapter {name!r}: {len(extra)} tensors do not belong to this base model (e.g. {extra[0]})")
+        if name in self.names:
+            sl = self.names.index(name)
+        elif None in self.names:
+            sl = self.names.index(None)
+        else:
+            raise ValueError(f"AdapterBank: all {self.slots} slots are taken ({self.loaded()}); unload one first")
+        master = {}
+        for li, grp, a, b in staged:
+            e = self.layers[li][grp]
+            e["b_img"][sl].copy_(b)
+            e["a_raw"][sl].copy_(a)
+            if e["a_raw"] is not e["a_img"]:
+                master[(li, grp)] = a
+        self.refresh()  # the other slots' folds and the recorded norm-weight keys are current first
+        self._master[sl] = master
+        self.names[sl] = name
+        self.version[sl] += 1
+        self._fold(sl)
+        return sl
+
+    @torch.no_grad()
+    def unload(self, name: str):
+        sl = self.slot(name)
+        for ent in self.layers:
+            for e in ent.values():
+                e["a_img"][sl].zero_()
+                e["b_img"][sl].zero_()
+                e["a_raw"][sl].zero_()
+        self._master.pop(sl, None)
+        self.names[sl] = None
+        self.version[sl] += 1
+
+    @torch.no_grad()
+    def _fold(self, sl: int, li: Optional[int] = None):
+        """a_img of the folded projections (of layer ``li``, or all) = bf16(s A diag(norm weight)) from
+        the fp32 master and the layer's current norm weight."""
+        for (l2, grp), a in self._master.get(sl, {}).items():
+            if li is None or l2 == li:
+                nw = getattr(self.model.layers[l2], "ln1_w" if grp == "qkv" else "ln2_w")
+                self.layers[l2][grp]["a_img"][sl].copy_(a * nw.detach().float().cpu()[None, :])
+
+    @torch.no_grad()
+    def refresh(self):
+        """Rebuild the folded a_img of every slot for each layer whose norm weights are not the ones
+        of its last fold (data pointer or in-place version: a checkpoint load, an optimizer step).
+        ``load`` and the batcher call it; call it after changing norm weights under a running batcher."""
+        for li, layer in enumerate(self.model.layers):
+            key = (layer.ln1_w.data_ptr(), layer.ln1_w._version, layer.ln2_w.data_ptr(), layer.ln2_w._version)
+            if self._fold_key.get(li) != key:
+                for sl in self._master:
+                    self._fold(sl, li)
+                self._fold_key[li] = key
+
+    # -------------------------------------------------------------- token-parallel path: one slot
+    @contextlib.contextmanager
+    def active(self, name: Optional[str]):
+        """Run the model's token-parallel forwards (prefill, scoring) with adapter ``name`` unmerged
+        — the K-extension GEMMs over this slot's images — or, for None, as the base model."""
+        sl = self.slot(name)
+        layers = self.model.layers
+        saved = [(layer.lora, layer.lora_enabled) for layer in layers]
+        if sl >= 0 and self._pf_slot != (sl, self.version[sl]):
+            R = self.R
+            with torch.no_grad():
+                for ent in self.layers:
+                    for e in ent.values():
+                        g = e["group"]
+                        nr = e["a_raw"].shape[1]
+                        g.merged_dirty = True  # a merged copy of another slot must never be reused
+                        g.a_pad[:nr].copy_(e["a_raw"][sl])
+                        bounds = list(g.col0) + [g.n_out]
+                        for i in range(len(g.col0)):
+                            g.ub[bounds[i]:bounds[i + 1], i * R:(i + 1) * R].copy_(e["b_img"][sl, bounds[i]:bounds[i + 1]])
+            self._pf_slot = (sl, self.version[sl])
+        try:
+            for layer, ent in zip(layers, self.layers):
+                layer.lora = {grp: e["group"] for grp, e in ent.items()} if sl >= 0 else {}
+                layer.lora_enabled = True
+            yield
+        finally:
+            for layer, (lo, en) in zip(layers, saved):
+                layer.lora, layer.lora_enabled = lo, en

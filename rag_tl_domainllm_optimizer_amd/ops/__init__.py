@@ -4,7 +4,7 @@ from ._ext import get_tuning, native, native_available, on_gpu, set_tuning, tuni
 from .linear import (  # noqa: F401
     ACT_DSWIGLU, ACT_IDS, ACT_SWIGLU, KMAJ, ROW, FoldCache, LoRAGroup, ShufCache, SplitK, gemm, gemm_big, gemm_decode, gemm_nn, gemm_tn, linear,
     swiglu_mlp, gemm_rope, linear_rope, rope_fusable,
-    refresh_lora_batched,
+    refresh_lora_batched, lora_rows_shrink,
     linear_deferred, batch_invariant)
 from .norm import layer_norm, rms_norm  # noqa: F401
 from .attention import (  # noqa: F401

@@ -852,8 +852,45 @@ def linear_deferred(x: torch.Tensor, w: torch.Tensor, bias=None, lora: Optional[
     return SplitK(slabs, s, M, N, x2.dtype)
 
 
+def lora_rows_shrink(x: torch.Tensor, a_img: torch.Tensor, ids: torch.Tensor, ks: int = 0, out=None) -> torch.Tensor:
+    """The shrink of per-row LoRA adapters in a decode step of at most 16 rows: fp32 slabs
+    ``T[z, b, :] = a_img[ids[b]] @ x[b]`` over K slice z for rows with ``ids[b] >= 0`` (other rows
+    are left unwritten and are never read). ``a_img`` [slots, nseg * R, K] bf16 holds ``s A`` of
+    every sub-projection (with the RMSNorm weight folded in where the base weight has it), ``ids``
+    int32 one adapter slot per row (< 0: base model). ``x`` is the raw input row: the in-GEMM RMS
+    factor is applied by the expand. Returns T [ks, 16, nseg * R]; the slices (``ks`` 0: a
+    function of K alone) are summed in slice order by ``gemm_decode(..., rows_lora=...)``."""
+    M = x.shape[0]
+    if M > 16:
+        raise ValueError(f"lora_rows_shrink: per-row adapters run at most 16 rows, got {M}")
+    if on_gpu(x):
+        return native().lora_rows_shrink(x.contiguous(), a_img, ids, ks, out)
+    t = torch.zeros(1, 16, a_img.shape[1], dtype=torch.float32) if out is None else out
+    for b, a in enumerate(ids[:M].tolist()):
+        if 0 <= a < a_img.shape[0]:
+            t[0, b] = a_img[a].float() @ x[b].float()
+    return t
+
+
+def _rows_lora_delta(rows_lora, M: int, N: int, pair: bool) -> torch.Tensor:
+    """Eager oracle of the adapter term: [M, N] fp32, zero on base rows (before the RMS factor)."""
+    t, b_img, ids, seg_bounds = rows_lora
+    R = b_img.shape[2]
+    tt = t.float().sum(0)  # K slices in slice order
+    bounds = [N // 2] if pair else [int(b) for b in seg_bounds]
+    seg = torch.zeros(N, dtype=torch.long)
+    for b in bounds:
+        seg += (torch.arange(N) >= b).long()
+    idx = seg[:, None] * R + torch.arange(R)[None, :]  # [N, R] columns of T each weight row reads
+    d = torch.zeros(M, N, dtype=torch.float32)
+    for b, a in enumerate(ids[:M].tolist()):
+        if 0 <= a < b_img.shape[0]:
+            d[b] = (tt[b].cpu()[idx] * b_img[a].float().cpu()).sum(-1)
+    return d
+
+
 def gemm_decode(x: torch.Tensor, w: torch.Tensor, act: int = 0, residual=None, norm_eps: float = 0.0, fp8=None,
-                shuf=None, fp4=None):
+                shuf=None, fp4=None, rows_lora=None):
     """Decode-step GEMM (M <= 64) with the fused prologue/epilogue of the skinny kernels:
     ``C = act(rstd(x) * x w^T) + residual`` where ``rstd`` (``norm_eps > 0``) is the RMS-norm of
     each input row computed inside the GEMM (the norm weight must already be folded into ``w``)
@@ -861,7 +898,17 @@ def gemm_decode(x: torch.Tensor, w: torch.Tensor, act: int = 0, residual=None, n
     ``shuf`` (ShufCache, M <= 16) streams the tile-ordered image of ``w`` instead. ``fp4``
     (Fp4Cache): at M <= 16 on a weight ``fp4_supported`` accepts, the MXFP4 image of ``w`` (W4A16
     16-row kernel on the GPU, the eager oracle over ``dequantize_mxfp4`` on the CPU); any other
-    case takes the path below on the bf16 weight."""
+    case takes the path below on the bf16 weight.
+
+    ``rows_lora`` = (T, b_img, ids, seg_bounds): per-row LoRA adapters (M <= 16). Row b adds
+    ``rstd_b * sum_j T[b, seg(n) R + j] * b_img[ids[b], n, j]`` to column n of the product before
+    the activation / SwiGLU pair (``T`` from :func:`lora_rows_shrink`; ``b_img`` [slots, N, R]
+    bf16; ``seg_bounds`` = first output column of sub-projections 1.., () for one, implied for
+    SwiGLU: gate 0, up 1). Rows with ``ids[b] < 0`` take the plain arithmetic bit for bit. On the
+    GPU this is always the 16-row kernel over the MXFP4, fp8 or tile-ordered bf16 image; the bf16
+    image needs its cache (``shuf``), also as the fall-back of an fp8 cache the shape does not fit."""
+    if rows_lora is not None:
+        return _gemm_decode_rows_lora(x, w, act, residual, norm_eps, fp8, shuf, fp4, rows_lora)
     if fp4 is not None and x.shape[0] <= 16:
         from .fp4 import dequantize_mxfp4, fp4_supported
 
@@ -890,6 +937,58 @@ def gemm_decode(x: torch.Tensor, w: torch.Tensor, act: int = 0, residual=None, n
     if act == ACT_SWIGLU:
         F = w.shape[0] // 2
         y = torch.nn.functional.silu(y[:, :F]) * y[:, F:]
+    else:
+        y = ref.apply_act(y, act)
+    if residual is not None:
+        y = y + residual.float()
+    return y.to(x.dtype)
+
+
+def _gemm_decode_rows_lora(x, w, act, residual, norm_eps, fp8, shuf, fp4, rows_lora):
+    t, b_img, ids, seg_bounds = rows_lora
+    M, K = x.shape
+    N = w.shape[0]
+    pair = act == ACT_SWIGLU
+    if M > 16:
+        raise ValueError(f"gemm_decode: per-row adapters (rows_lora) run at most 16 rows, got {M}")
+    R = b_img.shape[2]
+    nseg = t.shape[2] // R
+    if b_img.shape[1] != N or R not in (8, 16, 32, 64) or nseg * R != t.shape[2] or nseg * R > 192 \
+            or nseg != (2 if pair else len(seg_bounds) + 1):
+        raise ValueError(f"gemm_decode: rows_lora shapes do not fit: T {tuple(t.shape)}, b_img {tuple(b_img.shape)}, "
+                         f"N {N}, segments {tuple(seg_bounds)}")
+    from .fp4 import dequantize_mxfp4, fp4_supported
+
+    use_fp4 = fp4 is not None and fp4_supported(w, act)
+    if on_gpu(x):
+        if K % 64 or N % (64 if pair else 16):
+            raise ValueError(f"gemm_decode: rows_lora needs K % 64 == 0 and N % 16 == 0 (SwiGLU: 64), got N {N}, K {K}")
+        x = x.contiguous()
+        s1 = N if pair or nseg < 2 else int(seg_bounds[0])
+        s2 = N if pair or nseg < 3 else int(seg_bounds[1])
+        if use_fp4:
+            img, simg = fp4.image(w)
+            return native().gemv16_rows_lora(2, x, img, simg, act, residual, norm_eps, t, b_img, ids, s1, s2)
+        if fp8 is not None:
+            from .fp8 import fp8_supported
+
+            if fp8_supported(w) and fp8.shuf_ok(w, M, act):
+                qs, sc = fp8.shuf(w)
+                return native().gemv16_rows_lora(1, x, qs, sc, act, residual, norm_eps, t, b_img, ids, s1, s2)
+        if shuf is None:
+            # an image built per call would be re-shuffled by every replay of a captured step
+            raise ValueError("gemm_decode: rows_lora over bf16 weights needs the weight's ShufCache (shuf=...)")
+        img = shuf.get(w)
+        return native().gemv16_rows_lora(0, x, img, None, act, residual, norm_eps, t, b_img, ids, s1, s2)
+    if use_fp4:
+        w = dequantize_mxfp4(*fp4.get(w))
+    # eager oracle: fp32 products of the bf16 operands, the adapter term added to the base product
+    # before the RMS factor, then the plain epilogue; rounded to bf16 once, where the kernel rounds
+    y = x.float() @ w.float().t() + _rows_lora_delta(rows_lora, M, N, pair)
+    if norm_eps > 0:
+        y = y * torch.rsqrt(x.float().pow(2).mean(-1, keepdim=True) + norm_eps)
+    if pair:
+        y = torch.nn.functional.silu(y[:, :N // 2]) * y[:, N // 2:]
     else:
         y = ref.apply_act(y, act)
     if residual is not None:

@@ -34,7 +34,8 @@ def request_sampling(q, max_new_tokens: Optional[int] = None):
     return rs
 
 
-def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, per_request_sampling: bool = False):
+def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, per_request_sampling: bool = False,
+               adapters=None):
     import asyncio
 
     from fastapi import FastAPI, HTTPException
@@ -42,7 +43,9 @@ def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, pe
 
     if per_request_sampling and not continuous:
         raise ValueError("per_request_sampling needs continuous batching (continuous=True)")
-    engine = ContinuousEngine(pipeline, per_request_sampling=per_request_sampling) if continuous else \
+    if adapters is not None and not continuous:
+        raise ValueError("per-request adapters need continuous batching (continuous=True)")
+    engine = ContinuousEngine(pipeline, per_request_sampling=per_request_sampling, adapters=adapters) if continuous else \
         BatchingEngine(pipeline, max_wait_s=max_wait_s)
     app = FastAPI(title="rag-tl-domainllm-optimizer-amd")
     app.state.engine = engine
@@ -56,11 +59,13 @@ def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, pe
         do_sample: Optional[bool] = None
         seed: Optional[int] = None
         max_new_tokens: Optional[int] = None
+        adapter: Optional[str] = None  # a loaded LoRA adapter (servers with serve.adapters); None: the base model
 
     @app.get("/health")
     def health():
         return {"status": "ok", "docs": len(pipeline.docs), "max_batch": pipeline.max_batch,
-                "batching": "continuous" if continuous else "dynamic", "per_request_sampling": per_request_sampling}
+                "batching": "continuous" if continuous else "dynamic", "per_request_sampling": per_request_sampling,
+                "adapters": adapters.loaded() if adapters is not None else []}
 
     @app.get("/stats")
     def stats():
@@ -75,6 +80,14 @@ def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, pe
         if rs is not None and not per_request_sampling:
             raise HTTPException(status_code=400, detail="sampling settings in the request need the server flag "
                                                         "serve.per_request_sampling (off on this server)")
+        if q.adapter is not None:
+            if adapters is None:
+                raise HTTPException(status_code=400, detail="an adapter in the request needs a server started with "
+                                                            "serve.adapters (none on this server)")
+            if q.adapter not in adapters.loaded():
+                raise HTTPException(status_code=422, detail=f"unknown adapter {q.adapter!r}; loaded: {adapters.loaded()}")
+            a = await asyncio.wrap_future(engine.submit(q.query, q.top_k, rs, q.adapter))
+            return {"answer": a.answer, "doc_ids": a.doc_ids, "docs": a.docs, "scores": a.scores, "timings": a.timings}
         a = await asyncio.wrap_future(engine.submit(q.query, q.top_k, rs) if rs is not None else
                                       engine.submit(q.query, q.top_k))
         return {"answer": a.answer, "doc_ids": a.doc_ids, "docs": a.docs, "scores": a.scores, "timings": a.timings}
@@ -87,7 +100,7 @@ def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, pe
 
 
 def serve(cfg, host: str = "127.0.0.1", port: int = 8000, max_batch: int = 16, max_wait_s: float = 0.004,
-          continuous: bool = True, per_request_sampling: Optional[bool] = None):
+          continuous: bool = True, per_request_sampling: Optional[bool] = None, adapters=None):
     import uvicorn
 
     from ..cli import apply_fp4, build_stack
@@ -104,4 +117,21 @@ def serve(cfg, host: str = "127.0.0.1", port: int = 8000, max_batch: int = 16, m
                       cfg.ppo.max_prompt_tokens, max_batch=max_batch)
     if per_request_sampling is None:
         per_request_sampling = cfg.serve.per_request_sampling
-    uvicorn.run(create_app(rag, max_wait_s, continuous, per_request_sampling), host=host, port=port)
+    # per-request adapters: serve.adapters {name: PEFT directory}, plus / overridden by ``adapters``
+    named = dict(getattr(cfg.serve, "adapters", None) or {})
+    named.update(adapters or {})
+    bank = None
+    if named:
+        from ..models import AdapterBank
+        from ..models.lora import LoraConfig
+        import json
+        import os
+
+        ranks = []
+        for path in named.values():
+            with open(os.path.join(path, "adapter_config.json")) as f:
+                ranks.append(int(json.load(f).get("r", LoraConfig.r)))
+        bank = AdapterBank(st["policy"], slots=max(8, len(named)), r_max=next(r for r in (8, 16, 32, 64) if r >= max(ranks)))
+        for name, path in named.items():
+            bank.load(name, path)
+    uvicorn.run(create_app(rag, max_wait_s, continuous, per_request_sampling, bank), host=host, port=port)

@@ -15,6 +15,10 @@ Same client API as ``BatchingEngine``: ``submit`` -> Future[RagAnswer], ``answer
 temperature, top-k, top-p, greedy flag, seed and answer length inside the shared batch
 (``ContinuousBatcher(per_request=True)``); ``timings["seed"]`` is the seed the answer was drawn
 with, so a client can ask for the same answer again.
+
+``adapters=bank`` (``models.AdapterBank``): ``submit(..., adapter="name")`` answers with that loaded
+LoRA adapter over the shared base weights, beside rows of other adapters or of the base model
+(``ContinuousBatcher(adapters=bank)``, at most 16 rows); ``timings["adapter"]`` reports it.
 """
 from __future__ import annotations
 
@@ -32,7 +36,7 @@ from ..rag.prompt import extract_answer
 
 
 class ContinuousEngine:
-    def __init__(self, pipeline, chunk: int = 4, per_request_sampling: bool = False):
+    def __init__(self, pipeline, chunk: int = 4, per_request_sampling: bool = False, adapters=None):
         if pipeline.sampling.lookup_tokens > 0:
             raise NotImplementedError("prompt-lookup decoding is not supported with continuous batching")
         layers = getattr(pipeline.gen.model, "layers", None)
@@ -42,6 +46,7 @@ class ContinuousEngine:
         self.pipeline = pipeline
         self.chunk = max(1, chunk)
         self.per_request_sampling = bool(per_request_sampling)
+        self.adapters = adapters
         self._q: "queue.Queue" = queue.Queue()
         self._closed = False
         self._dead: Optional[BaseException] = None  # the error that ended the worker, if any
@@ -58,7 +63,11 @@ class ContinuousEngine:
 
     # ---------------------------------------------------------------- client side
     def submit(self, query: str, top_k: Optional[int] = None,
-               sampling: Optional[RequestSampling] = None) -> cf.Future:
+               sampling: Optional[RequestSampling] = None, adapter: Optional[str] = None) -> cf.Future:
+        if adapter is not None:
+            if self.adapters is None:
+                raise ValueError("an adapter in the request needs ContinuousEngine(adapters=bank)")
+            self.adapters.slot(adapter)  # KeyError for a name that is not loaded
         if sampling is not None:
             if not self.per_request_sampling:
                 raise ValueError("per-request sampling settings need ContinuousEngine(per_request_sampling=True)")
@@ -69,7 +78,7 @@ class ContinuousEngine:
                     raise RuntimeError(f"ContinuousEngine worker failed: {self._dead!r}") from self._dead
                 raise RuntimeError("ContinuousEngine is closed")
             fut: cf.Future = cf.Future()
-            self._q.put((query, top_k, fut, time.perf_counter(), sampling))
+            self._q.put((query, top_k, fut, time.perf_counter(), sampling, adapter))
         return fut
 
     @property
@@ -77,8 +86,8 @@ class ContinuousEngine:
         return not self._closed and self._worker.is_alive()
 
     def answer(self, query: str, top_k: Optional[int] = None, timeout: Optional[float] = None,
-               sampling: Optional[RequestSampling] = None) -> RagAnswer:
-        return self.submit(query, top_k, sampling).result(timeout)
+               sampling: Optional[RequestSampling] = None, adapter: Optional[str] = None) -> RagAnswer:
+        return self.submit(query, top_k, sampling, adapter).result(timeout)
 
     def answer_many(self, queries: List[str], timeout: Optional[float] = None) -> List[RagAnswer]:
         futs = [self.submit(q) for q in queries]
@@ -114,7 +123,7 @@ class ContinuousEngine:
                 it[2].set_exception(e)
             return
         t1 = time.perf_counter()
-        prompts, metas, samplings = [], [], []
+        prompts, metas, samplings, names = [], [], [], []
         for it, row_ids, row_sc in zip(live, ids_l, sc_l):
             docs = [p.docs[i] for i in row_ids if i >= 0]
             prompt = p._prompt_ids(it[0], docs)
@@ -123,6 +132,7 @@ class ContinuousEngine:
                 continue
             prompts.append(prompt)
             samplings.append(it[4])
+            names.append(it[5])
             metas.append({"query": it[0], "fut": it[2], "t_submit": it[3], "t_admit": time.perf_counter(),
                           "retrieve_s": t1 - t0, "doc_ids": row_ids, "docs": docs, "scores": row_sc,
                           "rows0": (self._row_steps, self.stats["steps"])})
@@ -130,7 +140,8 @@ class ContinuousEngine:
             return
         try:
             # consecutive free rows share one prefill
-            cb.admit_many(prompts, metas, samplings if self.per_request_sampling else None)
+            cb.admit_many(prompts, metas, samplings if self.per_request_sampling else None,
+                          names if self.adapters is not None else None)
         except BaseException as e:  # noqa: BLE001
             for m in metas:
                 m["fut"].set_exception(e)
@@ -153,6 +164,8 @@ class ContinuousEngine:
                    "batch_size": (self._row_steps - rs0) / steps if steps > 0 else 0.0}
             if r.seed is not None:
                 tim["seed"] = r.seed
+            if self.adapters is not None:
+                tim["adapter"] = r.adapter
             m["fut"].set_result(RagAnswer(m["query"], text, m["doc_ids"], m["docs"], m["scores"], tim))
             self.stats["finished"] += 1
 
@@ -160,7 +173,7 @@ class ContinuousEngine:
         p = self.pipeline
         try:
             cb = ContinuousBatcher(p.gen, p.sampling, pad_id=p.tok.pad_token_id, eos_ids=[p.tok.eos_token_id],
-                                   per_request=self.per_request_sampling)
+                                   per_request=self.per_request_sampling, adapters=self.adapters)
         except BaseException as e:  # noqa: BLE001
             self._init_error = e
             self._ready.set()
