@@ -77,7 +77,7 @@ int rt_logprob_bwd(const void*, int, long, const long*, float, long, int, const 
 int rt_sample(const void*, int, long, long, int, float, int, float, int, uint64_t, const int64_t*, const uint8_t*, long*,
               float*, hipStream_t);
 int rt_sample_rows(const void*, int, long, long, int, const float*, const int*, const float*, const uint8_t*,
-                   const int64_t*, const int*, const uint8_t*, long*, float*, hipStream_t);
+                   const int64_t*, const int*, const uint8_t*, long*, float*, int, hipStream_t);
 int rt_grad_sumsq(const float*, long, float*, int, hipStream_t);
 int rt_adamw(float*, const float*, float*, float*, void*, long, float, float, float, float, float, int, float,
              const float*, int, float*, int*, hipStream_t);
@@ -108,9 +108,9 @@ int rt_attn_verify(const void*, long, void*, void*, int, const int*, const int*,
                    const float*, float, int, void*, long, int, int, int, int, int, float, int, hipStream_t);
 int rt_lookup_accept(const long*, const float*, const long*, const int*, int, long*, float*, int, long*, int, uint8_t*,
                      int*, int*, int*, const int*, int*, int64_t*, int64_t*, unsigned long long*, int, const long*, int,
-                     hipStream_t);
+                     const int*, int*, hipStream_t);
 int rt_lookup_draft(const long*, int, const int*, const int*, const uint8_t*, int, int, long, long*, int*, uint8_t*, int,
-                    hipStream_t);
+                    const int*, hipStream_t);
 }
 
 namespace {
@@ -1284,31 +1284,38 @@ void sample(const Tensor& logits, double inv_temp, int64_t top_k, double top_p, 
 
 // Per-row sampling parameters, all [B] device tensors read by the kernels (a captured graph sees
 // new values on replay); the Philox stream of row b is keyed by (seed[b], counter[b]) alone.
+// group = G > 1: logits [B * G, V], parameters [B]; row r reads request r / G and draws with the
+// counter counter[r / G] + r % G; the row mask and the outputs stay per logits row.
 void sample_rows(const Tensor& logits, const Tensor& inv_temp, const Tensor& top_k, const Tensor& top_p,
                  const Tensor& greedy, const Tensor& seed, const Tensor& counter, const optional<Tensor>& active,
-                 Tensor out_tok, const optional<Tensor>& out_logp) {
+                 Tensor out_tok, const optional<Tensor>& out_logp, int64_t group) {
   CHECK_CUDA(logits); CHECK_ROWS(logits); CHECK_I64(out_tok);
   TORCH_CHECK(logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16,
               "sample_rows: logits must be float32 or bfloat16");
   const bool f32 = logits.scalar_type() == at::kFloat;
-  const int64_t B = logits.size(0);
+  const int64_t R = logits.size(0);
+  TORCH_CHECK(group >= 1 && group <= 8 && R % group == 0, "sample_rows: group must be in [1, 8] and divide the logits rows");
+  const int64_t B = R / group;
   CHECK_F32(inv_temp); CHECK_I32(top_k); CHECK_F32(top_p); CHECK_I64(seed); CHECK_I32(counter);
   TORCH_CHECK(greedy.scalar_type() == at::kByte || greedy.scalar_type() == at::kBool, "greedy must be uint8 or bool");
-  auto row_vec = [&](const Tensor& t, const char* name) {
+  // parameters: one entry per request ([B]); mask and outputs: one per logits row ([B * group])
+  auto vec = [&](const Tensor& t, const char* name, int64_t n) {
     TORCH_CHECK(t.is_cuda() && t.get_device() == logits.get_device(), "sample_rows: ", name, " must be on the logits' device");
-    TORCH_CHECK(t.dim() == 1 && t.is_contiguous() && t.numel() == B, "sample_rows: ", name, " must be contiguous [B]");
+    TORCH_CHECK(t.dim() == 1 && t.is_contiguous() && t.numel() == n, "sample_rows: ", name, " must be contiguous [",
+                n == B ? "B" : "B * group", "]");
   };
+  auto row_vec = [&](const Tensor& t, const char* name) { vec(t, name, B); };
   row_vec(inv_temp, "inv_temp"); row_vec(top_k, "top_k"); row_vec(top_p, "top_p"); row_vec(greedy, "greedy");
-  row_vec(seed, "seed"); row_vec(counter, "counter"); row_vec(out_tok, "out_tok");
+  row_vec(seed, "seed"); row_vec(counter, "counter"); vec(out_tok, "out_tok", R);
   if (active.has_value() && active->defined()) {
     TORCH_CHECK(active->scalar_type() == at::kByte || active->scalar_type() == at::kBool, "active must be uint8 or bool");
-    row_vec(*active, "active");
+    vec(*active, "active", R);
   }
-  if (out_logp.has_value() && out_logp->defined()) { CHECK_F32(*out_logp); row_vec(*out_logp, "out_logp"); }
-  check_rc(rt_sample_rows(logits.data_ptr(), f32, logits.stride(0), B, (int)logits.size(1), inv_temp.data_ptr<float>(),
+  if (out_logp.has_value() && out_logp->defined()) { CHECK_F32(*out_logp); vec(*out_logp, "out_logp", R); }
+  check_rc(rt_sample_rows(logits.data_ptr(), f32, logits.stride(0), R, (int)logits.size(1), inv_temp.data_ptr<float>(),
                           top_k.data_ptr<int>(), top_p.data_ptr<float>(), (const uint8_t*)greedy.data_ptr(),
                           (const int64_t*)seed.data_ptr(), counter.data_ptr<int>(), (const uint8_t*)opt_ptr(active),
-                          (long*)out_tok.data_ptr(), (float*)opt_ptr(out_logp), cur_stream()),
+                          (long*)out_tok.data_ptr(), (float*)opt_ptr(out_logp), (int)group, cur_stream()),
            "sample_rows");
 }
 
@@ -1620,7 +1627,8 @@ void attn_verify(const Tensor& qkv, Tensor kc, Tensor vc, const Tensor& slot0, c
 void lookup_accept(const Tensor& sampled, const Tensor& logp, const Tensor& inp, const Tensor& n_draft,
                    Tensor out_tokens, Tensor out_logp, Tensor hist, Tensor active, Tensor kv_len, Tensor pos,
                    Tensor attn_len, const Tensor& kv_start, Tensor gen_len, Tensor step, Tensor rng_offset,
-                   Tensor counters, const Tensor& eos_ids) {
+                   Tensor counters, const Tensor& eos_ids, const optional<Tensor>& row_max_new,
+                   const optional<Tensor>& row_stats) {
   CHECK_CUDA(sampled); CHECK_I64(sampled); CHECK_F32(logp); CHECK_I64(inp); CHECK_I32(n_draft); CHECK_I64(out_tokens);
   CHECK_F32(out_logp); CHECK_I64(hist); CHECK_I32(kv_len); CHECK_I32(pos); CHECK_I32(attn_len); CHECK_I32(kv_start);
   CHECK_I32(gen_len); CHECK_I64(step); CHECK_I64(rng_offset); CHECK_I64(counters); CHECK_I64(eos_ids);
@@ -1634,6 +1642,18 @@ void lookup_accept(const Tensor& sampled, const Tensor& logp, const Tensor& inp,
   TORCH_CHECK(hist.dim() == 2 && hist.is_contiguous() && hist.size(0) >= B, "lookup_accept: hist [B, Smax]");
   TORCH_CHECK(active.numel() >= B && kv_len.numel() >= B && pos.numel() >= B && attn_len.numel() >= B &&
                   kv_start.numel() >= B && gen_len.numel() >= B && counters.numel() >= 3, "lookup_accept: state");
+  const bool has_max = row_max_new.has_value() && row_max_new->defined();
+  const bool has_stats = row_stats.has_value() && row_stats->defined();
+  if (has_max) {
+    CHECK_I32(*row_max_new);
+    TORCH_CHECK(row_max_new->is_cuda() && row_max_new->is_contiguous() && row_max_new->numel() == B,
+                "lookup_accept: row_max_new [B]");
+  }
+  if (has_stats) {
+    CHECK_I32(*row_stats);
+    TORCH_CHECK(row_stats->is_cuda() && row_stats->is_contiguous() && row_stats->dim() == 2 &&
+                    row_stats->size(0) == B && row_stats->size(1) == 2, "lookup_accept: row_stats [B, 2]");
+  }
   check_rc(rt_lookup_accept((const long*)sampled.data_ptr(), logp.data_ptr<float>(), (const long*)inp.data_ptr(),
                             n_draft.data_ptr<int>(), (int)G, (long*)out_tokens.data_ptr(), out_logp.data_ptr<float>(),
                             (int)out_tokens.size(1), (long*)hist.data_ptr(), (int)hist.size(1),
@@ -1641,13 +1661,14 @@ void lookup_accept(const Tensor& sampled, const Tensor& logp, const Tensor& inp,
                             attn_len.data_ptr<int>(), kv_start.data_ptr<int>(), gen_len.data_ptr<int>(),
                             (int64_t*)step.data_ptr(), (int64_t*)rng_offset.data_ptr(),
                             (unsigned long long*)counters.data_ptr(), (int)B, (const long*)eos_ids.data_ptr(),
-                            (int)eos_ids.numel(), cur_stream()),
+                            (int)eos_ids.numel(), has_max ? row_max_new->data_ptr<int>() : nullptr,
+                            has_stats ? row_stats->data_ptr<int>() : nullptr, cur_stream()),
            "lookup_accept");
 }
 
 // The next verify step's inputs: last emitted token + the n-gram lookup draft (one workgroup per row).
 void lookup_draft(const Tensor& hist, const Tensor& kv_len, const Tensor& kv_start, const Tensor& active, int64_t ngram,
-                  int64_t pad_id, Tensor inp, Tensor n_draft, Tensor row_active) {
+                  int64_t pad_id, Tensor inp, Tensor n_draft, Tensor row_active, const optional<Tensor>& row_draft) {
   CHECK_CUDA(hist); CHECK_I64(hist); CHECK_I32(kv_len); CHECK_I32(kv_start); CHECK_I64(inp); CHECK_I32(n_draft);
   TORCH_CHECK(active.scalar_type() == at::kByte && row_active.scalar_type() == at::kByte, "lookup_draft: uint8 flags");
   TORCH_CHECK(inp.dim() == 2 && inp.is_contiguous() && hist.dim() == 2 && hist.is_contiguous(), "lookup_draft: layout");
@@ -1655,10 +1676,16 @@ void lookup_draft(const Tensor& hist, const Tensor& kv_len, const Tensor& kv_sta
   TORCH_CHECK(hist.size(0) >= B && kv_len.numel() >= B && kv_start.numel() >= B && active.numel() >= B &&
                   n_draft.numel() >= B && row_active.numel() >= B * G && row_active.is_contiguous(),
               "lookup_draft: state");
+  const bool has_draft = row_draft.has_value() && row_draft->defined();
+  if (has_draft) {
+    CHECK_I32(*row_draft);
+    TORCH_CHECK(row_draft->is_cuda() && row_draft->is_contiguous() && row_draft->numel() == B,
+                "lookup_draft: row_draft [B]");
+  }
   check_rc(rt_lookup_draft((const long*)hist.data_ptr(), (int)hist.size(1), kv_len.data_ptr<int>(),
                            kv_start.data_ptr<int>(), (const uint8_t*)active.data_ptr(), (int)G, (int)ngram, (long)pad_id,
                            (long*)inp.data_ptr(), n_draft.data_ptr<int>(), (uint8_t*)row_active.data_ptr(), (int)B,
-                           cur_stream()),
+                           has_draft ? row_draft->data_ptr<int>() : nullptr, cur_stream()),
            "lookup_draft");
 }
 
@@ -1747,7 +1774,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("logprob_fwd", &logprob_fwd);
   m.def("logprob_bwd", &logprob_bwd);
   m.def("sample", &sample);
-  m.def("sample_rows", &sample_rows);
+  m.def("sample_rows", &sample_rows, py::arg("logits"), py::arg("inv_temp"), py::arg("top_k"), py::arg("top_p"),
+        py::arg("greedy"), py::arg("seed"), py::arg("counter"), py::arg("active"), py::arg("out_tok"),
+        py::arg("out_logp"), py::arg("group") = 1);
   m.def("adamw", &adamw);
   m.def("scatter_scaled", &scatter_scaled, "batched scaled fp32 -> bf16 strided scatter (LoRA images)");
   m.def("lora_grad_accum", &lora_grad_accum, "LoRA backward: scaled sum of adapter-gradient slabs into grads");
@@ -1766,8 +1795,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_update", &decode_update);
   m.def("decode_update_rows", &decode_update_rows);
   m.def("attn_verify", &attn_verify, "verify step: RoPE + KV append + attention of G consecutive positions per row");
-  m.def("lookup_accept", &lookup_accept, "prompt-lookup decoding: accept / emit bookkeeping of a verify step");
-  m.def("lookup_draft", &lookup_draft, "prompt-lookup decoding: next inputs = last token + n-gram draft");
+  m.def("lookup_accept", &lookup_accept, "prompt-lookup decoding: accept / emit bookkeeping of a verify step",
+        py::arg("sampled"), py::arg("logp"), py::arg("inp"), py::arg("n_draft"), py::arg("out_tokens"),
+        py::arg("out_logp"), py::arg("hist"), py::arg("active"), py::arg("kv_len"), py::arg("pos"), py::arg("attn_len"),
+        py::arg("kv_start"), py::arg("gen_len"), py::arg("step"), py::arg("rng_offset"), py::arg("counters"),
+        py::arg("eos_ids"), py::arg("row_max_new") = py::none(), py::arg("row_stats") = py::none());
+  m.def("lookup_draft", &lookup_draft, "prompt-lookup decoding: next inputs = last token + n-gram draft",
+        py::arg("hist"), py::arg("kv_len"), py::arg("kv_start"), py::arg("active"), py::arg("ngram"), py::arg("pad_id"),
+        py::arg("inp"), py::arg("n_draft"), py::arg("row_active"), py::arg("row_draft") = py::none());
   ragtl::bind_tokenizer(m);
   ragtl::bind_ivf_host(m);
 }

@@ -153,6 +153,10 @@ __global__ void decode_update_kernel(const long* __restrict__ tok, long* __restr
 // sits at hist[kv_len], the slot the next step appends it at). Lengths advance by the emitted count.
 // counters: {row-steps, drafted tokens, accepted tokens that were emitted} (integer atomics: the sum
 // does not depend on thread order). One thread per row, one workgroup.
+// `row_max_new` (optional, [B]): the row's own answer length; it finishes at min(row_max_new[b],
+// max_new), as in decode_update_kernel. `row_stats` (optional, [B, 2] int32): per row {verify steps
+// it was active in, accepted tokens emitted}, added by the row's own thread (plain load / add /
+// store; zeroed by the host when a request is admitted into the row).
 __global__ void lookup_accept_kernel(const long* __restrict__ sampled, const float* __restrict__ logp,
                                      const long* __restrict__ inp, const int* __restrict__ n_draft, int G,
                                      long* __restrict__ out_tokens, float* __restrict__ out_logp, int max_new,
@@ -161,12 +165,14 @@ __global__ void lookup_accept_kernel(const long* __restrict__ sampled, const flo
                                      const int* __restrict__ kv_start, int* __restrict__ gen_len,
                                      int64_t* __restrict__ step, int64_t* __restrict__ rng_offset,
                                      unsigned long long* __restrict__ counters, int B,
-                                     const long* __restrict__ eos_ids, int n_eos) {
+                                     const long* __restrict__ eos_ids, int n_eos,
+                                     const int* __restrict__ row_max_new, int* __restrict__ row_stats) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t s = *step;
   if (b < B) {
     const int gl = gen_len[b], kl = kv_len[b];
     if (active[b] != 0 && gl < max_new) {
+      const int lim = row_max_new ? min(row_max_new[b], max_new) : max_new;
       const int nd = min(max(n_draft[b], 0), G - 1);
       int a = 0;
       while (a < nd && sampled[(long)b * G + a] == inp[(long)b * G + a + 1]) ++a;
@@ -178,7 +184,7 @@ __global__ void lookup_accept_kernel(const long* __restrict__ sampled, const flo
         out_logp[(long)b * max_new + gl + i] = logp[(long)b * G + i];
         if (kl + 1 + i < Smax) hist[(long)b * Smax + kl + 1 + i] = t;
         e = i + 1;
-        fin = gl + e >= max_new;
+        fin = gl + e >= lim;
         for (int q = 0; q < n_eos; ++q) fin = fin || (t == eos_ids[q]);
       }
       gen_len[b] = gl + e;
@@ -187,6 +193,10 @@ __global__ void lookup_accept_kernel(const long* __restrict__ sampled, const flo
       atomicAdd(counters + 0, 1ull);
       atomicAdd(counters + 1, (unsigned long long)nd);
       atomicAdd(counters + 2, (unsigned long long)(e - 1));
+      if (row_stats) {
+        row_stats[2 * b] += 1;
+        row_stats[2 * b + 1] += e - 1;
+      }
     }
     const int kn = kv_len[b];
     attn_len[b] = kn + 1;
@@ -206,13 +216,16 @@ __global__ void lookup_accept_kernel(const long* __restrict__ sampled, const flo
 // how many exist (0: nothing matched), the rest is pad. The latest start is a max-reduction over
 // the candidates (block_max over per-thread maxima: independent of thread order). row_active
 // [B, G] = the row's active flag per position (the sampler's row mask). Inactive rows get pad.
+// `row_draft` (optional, [B]): the row's own draft length, capping the proposal at
+// min(row_draft[b], G - 1) tokens; 0: an empty draft, the verify step emits one token for the row.
 __global__ __launch_bounds__(256) void lookup_draft_kernel(const long* __restrict__ hist, int Smax,
                                                            const int* __restrict__ kv_len,
                                                            const int* __restrict__ kv_start,
                                                            const uint8_t* __restrict__ active, int G, int ngram,
                                                            long pad_id, long* __restrict__ inp,
                                                            int* __restrict__ n_draft,
-                                                           uint8_t* __restrict__ row_active) {
+                                                           uint8_t* __restrict__ row_active,
+                                                           const int* __restrict__ row_draft) {
   __shared__ int red[4];
   __shared__ int best_sh;
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -248,7 +261,8 @@ __global__ __launch_bounds__(256) void lookup_draft_kernel(const long* __restric
     __syncthreads();  // red / best_sh are rewritten by the next n
   }
   const int cont = best + bn;  // first proposed token
-  const int avail = best >= 0 ? min(G - 1, end - cont) : 0;
+  const int cap = row_draft ? min(max(row_draft[b], 0), G - 1) : G - 1;
+  const int avail = best >= 0 ? min(cap, end - cont) : 0;
   if (tid == 0) {
     in[0] = h[kl];
     n_draft[b] = avail;
@@ -260,23 +274,24 @@ extern "C" int rt_lookup_accept(const long* sampled, const float* logp, const lo
                                 long* out_tokens, float* out_logp, int max_new, long* hist, int Smax,
                                 uint8_t* active, int* kv_len, int* pos, int* attn_len, const int* kv_start,
                                 int* gen_len, int64_t* step, int64_t* rng_offset, unsigned long long* counters, int B,
-                                const long* eos_ids, int n_eos, hipStream_t stream) {
+                                const long* eos_ids, int n_eos, const int* row_max_new, int* row_stats,
+                                hipStream_t stream) {
   if (B > 1024 || G < 1 || G > 8) return -1;
   if (B == 0) return 0;
   hipLaunchKernelGGL(lookup_accept_kernel, dim3(1), dim3(((B + 63) / 64) * 64), 0, stream, sampled, logp, inp,
                      n_draft, G, out_tokens, out_logp, max_new, hist, Smax, active, kv_len, pos, attn_len, kv_start,
-                     gen_len, step, rng_offset, counters, B, eos_ids, n_eos);
+                     gen_len, step, rng_offset, counters, B, eos_ids, n_eos, row_max_new, row_stats);
   RT_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int rt_lookup_draft(const long* hist, int Smax, const int* kv_len, const int* kv_start,
                                const uint8_t* active, int G, int ngram, long pad_id, long* inp, int* n_draft,
-                               uint8_t* row_active, int B, hipStream_t stream) {
+                               uint8_t* row_active, int B, const int* row_draft, hipStream_t stream) {
   if (G < 1 || G > 8 || ngram < 1) return -1;
   if (B == 0) return 0;
   hipLaunchKernelGGL(lookup_draft_kernel, dim3((unsigned)B), dim3(256), 0, stream, hist, Smax, kv_len, kv_start,
-                     active, G, ngram, pad_id, inp, n_draft, row_active);
+                     active, G, ngram, pad_id, inp, n_draft, row_active, row_draft);
   RT_LAUNCH_CHECK();
   return 0;
 }

@@ -907,6 +907,13 @@ __global__ __launch_bounds__(1024) void sample_topk_search_kernel(
 // row runs is a workgroup-uniform branch: rows with 1 <= top_k <= 1024 that draw take the
 // 1024-thread search body (sample_rows_search_kernel, when the logits qualify for it), every other
 // row the 256-thread radix body; each kernel's workgroups of the other kind exit at once.
+//
+// Groups (the verify step of prompt-lookup decoding in the continuous batch): `group` = G logits
+// rows per request, the parameter arrays hold one entry per request. Row r reads the parameters of
+// request r / G and draws with the counter counter[r / G] + r % G: with counter = the request's
+// generated length, position j draws what the plain per-row step draws for output index
+// gen_len + j, so a request's stream stays a function of (seed, generated index) alone. The row
+// mask and the outputs are per logits row. group = 1 is the plain per-row launch.
 // ---------------------------------------------------------------------------------------------
 struct RowParams {
   const float* inv_temp;
@@ -915,22 +922,24 @@ struct RowParams {
   const uint8_t* greedy;
   const int64_t* seed;
   const int* counter;
+  int group;
 };
-__device__ __forceinline__ bool row_takes_search(const RowParams& p, long row) {
-  const int k = p.top_k[row];
-  return !p.greedy[row] && k >= 1 && k <= 1024;
+__device__ __forceinline__ bool row_takes_search(const RowParams& p, long req) {
+  const int k = p.top_k[req];
+  return !p.greedy[req] && k >= 1 && k <= 1024;
 }
 
 __global__ __launch_bounds__(1024) void sample_rows_search_kernel(const bf16_t* __restrict__ logits, long ld, int V,
                                                                   RowParams p, const uint8_t* __restrict__ row_active,
                                                                   long* __restrict__ out_tok,
                                                                   float* __restrict__ out_logp, int flags) {
-  const long row = blockIdx.x;
-  if (!row_takes_search(p, row)) return;
+  const long row = blockIdx.x, req = blockIdx.x / (unsigned)p.group;  // 32-bit divide, once per workgroup
+  if (!row_takes_search(p, req)) return;
   const int* counter = p.counter;
-  sample_row_search(logits + row * ld, row, 0ull, V, p.inv_temp[row], p.top_k[row], p.top_p[row],
-                    (uint64_t)p.seed[row], [=]() -> uint64_t { return (uint64_t)counter[row]; }, row_active, out_tok,
-                    out_logp, flags);
+  const uint64_t j = (uint64_t)(row - req * p.group);
+  sample_row_search(logits + row * ld, row, 0ull, V, p.inv_temp[req], p.top_k[req], p.top_p[req],
+                    (uint64_t)p.seed[req], [=]() -> uint64_t { return (uint64_t)counter[req] + j; }, row_active,
+                    out_tok, out_logp, flags);
 }
 
 // LDS = true: bf16 rows staged as 16-bit keys (sample_row_bf16_lds); search_rows: the launch is
@@ -941,16 +950,17 @@ __global__ __launch_bounds__(256) void sample_rows_radix_kernel(const T* __restr
                                                                 const uint8_t* __restrict__ row_active,
                                                                 long* __restrict__ out_tok,
                                                                 float* __restrict__ out_logp) {
-  const long row = blockIdx.x;
-  if (search_rows && row_takes_search(p, row)) return;
+  const long row = blockIdx.x, req = blockIdx.x / (unsigned)p.group;  // 32-bit divide, once per workgroup
+  if (search_rows && row_takes_search(p, req)) return;
   const int* counter = p.counter;
-  auto offp = [=]() -> uint64_t { return (uint64_t)counter[row]; };
+  const uint64_t j = (uint64_t)(row - req * p.group);
+  auto offp = [=]() -> uint64_t { return (uint64_t)counter[req] + j; };
   if constexpr (LDS)
-    sample_row_bf16_lds(logits + row * ld, row, 0ull, V, p.inv_temp[row], p.top_k[row], p.top_p[row],
-                        (int)p.greedy[row], (uint64_t)p.seed[row], offp, row_active, out_tok, out_logp);
+    sample_row_bf16_lds(logits + row * ld, row, 0ull, V, p.inv_temp[req], p.top_k[req], p.top_p[req],
+                        (int)p.greedy[req], (uint64_t)p.seed[req], offp, row_active, out_tok, out_logp);
   else
-    sample_row_radix<T>(logits + row * ld, row, 0ull, V, p.inv_temp[row], p.top_k[row], p.top_p[row],
-                        (int)p.greedy[row], (uint64_t)p.seed[row], offp, row_active, out_tok, out_logp);
+    sample_row_radix<T>(logits + row * ld, row, 0ull, V, p.inv_temp[req], p.top_k[req], p.top_p[req],
+                        (int)p.greedy[req], (uint64_t)p.seed[req], offp, row_active, out_tok, out_logp);
 }
 
 }  // namespace rt
@@ -989,9 +999,11 @@ extern "C" int rt_sample(const void* logits, int is_f32, long ld, long B, int V,
 extern "C" int rt_sample_rows(const void* logits, int is_f32, long ld, long B, int V, const float* inv_temp,
                               const int* top_k, const float* top_p, const uint8_t* greedy, const int64_t* seed,
                               const int* counter, const uint8_t* row_active, long* out_tok, float* out_logp,
-                              hipStream_t stream) {
+                              int group, hipStream_t stream) {
+  // B logits rows = B / group requests (the parameter arrays' length)
+  if (group < 1 || group > 8 || B % group) return -1;
   if (B == 0) return 0;
-  const RowParams p{inv_temp, top_k, top_p, greedy, seed, counter};
+  const RowParams p{inv_temp, top_k, top_p, greedy, seed, counter, group};
   const bool lds = !is_f32 && V % 8 == 0 && ld % 8 == 0 && (size_t)V * 2 <= 96 * 1024;
   if (lds) {
     const size_t shm = ((size_t)V * 2 + 15) / 16 * 16;

@@ -68,9 +68,22 @@ class RequestSampling:
     do_sample: Optional[bool] = None
     seed: Optional[int] = None
     max_new_tokens: Optional[int] = None
+    # draft tokens per verify step of this request, 0 .. the batcher's lookup_tokens (None: the
+    # batcher's); only for batchers with prompt-lookup decoding on
+    lookup_tokens: Optional[int] = None
 
-    def validate(self, max_new: Optional[int] = None):
-        """ValueError for a setting outside its range (``max_new``: the batcher's output width)."""
+    def validate(self, max_new: Optional[int] = None, lookup: Optional[int] = None):
+        """ValueError for a setting outside its range (``max_new``: the batcher's output width;
+        ``lookup``: the batcher's draft length K, 0 = lookup off, None = not checked here)."""
+        if self.lookup_tokens is not None:
+            if not (isinstance(self.lookup_tokens, int) and 0 <= self.lookup_tokens <= 7):
+                raise ValueError(f"lookup_tokens = {self.lookup_tokens}: must be an integer in [0, 7]")
+            if lookup == 0:
+                raise ValueError(f"lookup_tokens = {self.lookup_tokens}: prompt-lookup decoding is off on this batcher "
+                                 f"(ContinuousBatcher(lookup_tokens=K))")
+            if lookup is not None and self.lookup_tokens > lookup:
+                raise ValueError(f"lookup_tokens = {self.lookup_tokens}: must be in [0, {lookup}] (the batcher's "
+                                 f"lookup_tokens)")
         if self.temperature is not None and not self.temperature >= 0:
             raise ValueError(f"temperature = {self.temperature}: must be >= 0 (0 = greedy)")
         if self.top_k is not None and not self.top_k >= 0:
@@ -105,6 +118,16 @@ class _RowParams:
         self.greedy = torch.zeros(B, dtype=torch.uint8, device=device)
         self.seed = torch.zeros(B, dtype=torch.long, device=device)
         self.max_new = torch.ones(B, dtype=torch.int32, device=device)
+        # the row's own draft length (prompt-lookup decoding in the continuous batch): allocated by
+        # the first batcher that turns lookup on, read by the draft kernel only
+        self.row_draft = None
+
+    def draft_buffer(self, K: int):
+        """row_draft, every row at the batcher's K"""
+        if self.row_draft is None:
+            self.row_draft = torch.empty_like(self.max_new)
+        self.row_draft.fill_(K)
+        return self.row_draft
 
     def tensors(self):
         return [self.inv_temp, self.top_k, self.top_p, self.greedy, self.seed, self.max_new]
@@ -248,6 +271,9 @@ class Generator:
         self.hist = None
         self._lookup = {}
         self._lk = None
+        # True while a ContinuousBatcher with lookup_tokens > 0 owns the generator: the verify step
+        # then keeps per-row figures and, with per-request sampling, reads the row buffers
+        self._lk_rows = False
         # per-request sampling (ContinuousBatcher(per_request=True)): per-row parameter buffers,
         # allocated on first use; _rows_on selects the per-row sampler and bookkeeping in _emit
         self.rowp = None
@@ -309,6 +335,20 @@ class Generator:
         if self.value_head is not None:
             raise NotImplementedError("prompt-lookup decoding does not support a value head (PPO rollouts)")
 
+    def _check_verify_rows(self, rows: int, K: int, fused: bool = True):
+        """A verify step runs rows * (K + 1) rows through the decode layer: ValueError above the fused
+        layer's limit (``fused``: checked) or the 16 rows of the MXFP4 decode kernels."""
+        if fused:
+            layers = getattr(self.model, "layers", None)
+            fp8 = bool(layers) and getattr(layers[0], "fp8_enabled", False)
+            max_b = getattr(self.model, "fused_decode_max_batch_fp8" if fp8 else "fused_decode_max_batch", None)
+            if max_b is not None and rows * (K + 1) > max_b:
+                raise ValueError(f"prompt-lookup decoding: {rows} rows x {K + 1} positions exceed the fused "
+                                 f"decode layer's limit of {max_b} rows")
+        if _fp4_decode_on(self.model) and rows * (K + 1) > 16:
+            raise ValueError(f"prompt-lookup decoding: {rows} rows x {K + 1} positions exceed the 16 rows of the "
+                             f"MXFP4 decode kernels (model.fp4_decode)")
+
     def _step_verify(self, params: SamplingParams, eos_ids: torch.Tensor, pad_id: int):
         """One verify step: forward over G = K + 1 positions per row (the last emitted token and the
         draft), the ordinary sampler on every position, then the accept and draft bookkeeping."""
@@ -318,18 +358,39 @@ class Generator:
         h = self.model.decode_verify(st.inp[:nb], self.pos[:nb], self.kv_len[:nb], self.attn_len[:nb],
                                      self.kv_start[:nb], cache, self.workspace)
         logits = self.model.logits(h)
-        ops.sample(logits, params.inv_temp, params.top_k, params.top_p, params.greedy, params.seed,
-                   self.rng_offset, st.row_active[:nb * G], st.sampled[:nb * G], st.sampled_lp[:nb * G])
-        ops.lookup_accept(st.sampled[:nb * G], st.sampled_lp[:nb * G], st.inp[:nb], st.n_draft[:nb],
-                          self.out_tokens[:nb], self.out_logp[:nb], self.hist[:nb], self.active[:nb],
-                          self.kv_len[:nb], self.pos[:nb], self.attn_len[:nb], self.kv_start[:nb],
-                          self.gen_len[:nb], self.step, self.rng_offset, st.counters, eos_ids)
+        rp = self.rowp if (self._rows_on and self._lk_rows) else None
+        if rp is not None:
+            # G positions per request: position j draws with the counter of output index gen_len + j,
+            # the one the plain per-request step would use for that token
+            ops.sample_rows(logits, rp.inv_temp[:nb], rp.top_k[:nb], rp.top_p[:nb], rp.greedy[:nb], rp.seed[:nb],
+                            self.gen_len[:nb], st.row_active[:nb * G], st.sampled[:nb * G], st.sampled_lp[:nb * G],
+                            group=G)
+        else:
+            ops.sample(logits, params.inv_temp, params.top_k, params.top_p, params.greedy, params.seed,
+                       self.rng_offset, st.row_active[:nb * G], st.sampled[:nb * G], st.sampled_lp[:nb * G])
+        if self._lk_rows:
+            # continuous batch: per-row figures, and the row's own answer length under per-request sampling
+            ops.lookup_accept(st.sampled[:nb * G], st.sampled_lp[:nb * G], st.inp[:nb], st.n_draft[:nb],
+                              self.out_tokens[:nb], self.out_logp[:nb], self.hist[:nb], self.active[:nb],
+                              self.kv_len[:nb], self.pos[:nb], self.attn_len[:nb], self.kv_start[:nb],
+                              self.gen_len[:nb], self.step, self.rng_offset, st.counters, eos_ids,
+                              row_max_new=None if rp is None else rp.max_new[:nb], row_stats=st.row_stats[:nb])
+        else:
+            ops.lookup_accept(st.sampled[:nb * G], st.sampled_lp[:nb * G], st.inp[:nb], st.n_draft[:nb],
+                              self.out_tokens[:nb], self.out_logp[:nb], self.hist[:nb], self.active[:nb],
+                              self.kv_len[:nb], self.pos[:nb], self.attn_len[:nb], self.kv_start[:nb],
+                              self.gen_len[:nb], self.step, self.rng_offset, st.counters, eos_ids)
         self._draft(params, pad_id)
 
-    def _draft(self, params: SamplingParams, pad_id: int):
-        nb, st = self._nb, self._lk
-        ops.lookup_draft(self.hist[:nb], self.kv_len[:nb], self.kv_start[:nb], self.active[:nb],
-                         params.lookup_ngram, pad_id, st.inp[:nb], st.n_draft[:nb], st.row_active[:nb * st.G])
+    def _draft(self, params: SamplingParams, pad_id: int, r0: int = 0, r1: Optional[int] = None):
+        """The next verify step's inputs of rows [r0, r1) (default: the row bucket); every buffer is
+        sliced per row, so other rows' inputs, draft counts and row masks are not touched."""
+        st = self._lk
+        r1 = self._nb if r1 is None else r1
+        rd = self.rowp.row_draft[r0:r1] if (self._rows_on and self._lk_rows) else None
+        ops.lookup_draft(self.hist[r0:r1], self.kv_len[r0:r1], self.kv_start[r0:r1], self.active[r0:r1],
+                         params.lookup_ngram, pad_id, st.inp[r0:r1], st.n_draft[r0:r1],
+                         st.row_active[r0 * st.G:r1 * st.G], row_draft=rd)
 
     def _emit(self, h, params: SamplingParams, eos_ids, pad_id, r0: int = 0):
         """Sample from the hidden states of rows [r0, r0 + len(h)) and run the bookkeeping for them
@@ -432,6 +493,7 @@ class Generator:
             T = max(1, min(T, params.max_length - S))
         self._check_lookup(params)
         self._rows_on = False  # a batch under one SamplingParams: the scalar sampler and its stream
+        self._lk_rows = False
         K = params.lookup_tokens
         # the last verify step may append K rows past the last emitted token
         assert S + T + K <= self.max_seq, f"prompt {S} + new {T} (+ {K} draft) exceeds cache {self.max_seq}"
@@ -487,16 +549,8 @@ class Generator:
             self.model.prefill(ids, self.kv_start[:B], sub)
         K = params.lookup_tokens
         self._nb = self._bucket(B)
-        if K > 0 and dev.type == "cuda":
-            layers = getattr(self.model, "layers", None)
-            fp8 = bool(layers) and getattr(layers[0], "fp8_enabled", False)
-            max_b = getattr(self.model, "fused_decode_max_batch_fp8" if fp8 else "fused_decode_max_batch", None)
-            if max_b is not None and self._nb * (K + 1) > max_b:
-                raise ValueError(f"prompt-lookup decoding: {self._nb} rows x {K + 1} positions exceed the fused "
-                                 f"decode layer's limit of {max_b} rows")
-        if K > 0 and _fp4_decode_on(self.model) and self._nb * (K + 1) > 16:
-            raise ValueError(f"prompt-lookup decoding: {self._nb} rows x {K + 1} positions exceed the 16 rows of the "
-                             f"MXFP4 decode kernels (model.fp4_decode)")
+        if K > 0:
+            self._check_verify_rows(self._nb, K, fused=dev.type == "cuda")
         if hasattr(self.model, "refresh_decode_weights"):
             # folded / tile-ordered / fp8 images of graph replays; a verify step runs rows * (K + 1) rows
             self.model.refresh_decode_weights(self._nb * (K + 1))
@@ -698,9 +752,12 @@ class _LookupState:
         self.sampled = torch.zeros(B * G, dtype=torch.long, device=device)
         self.sampled_lp = torch.zeros(B * G, dtype=torch.float32, device=device)
         self.counters = torch.zeros(3, dtype=torch.long, device=device)         # row-steps, drafted, accepted
+        # continuous batch: per row (verify steps it was active in, accepted tokens emitted)
+        self.row_stats = torch.zeros(B, 2, dtype=torch.int32, device=device)
 
     def tensors(self):
-        return [self.inp, self.n_draft, self.row_active, self.sampled, self.sampled_lp, self.counters]
+        return [self.inp, self.n_draft, self.row_active, self.sampled, self.sampled_lp, self.counters,
+                self.row_stats]
 
 
 class _SubCache:
@@ -781,6 +838,10 @@ class FinishedRow:
     steps_waited: int
     seed: Optional[int] = None  # per-request sampling: the seed the row drew with (given or derived)
     adapter: Optional[str] = None  # per-request adapters: the adapter the row ran with (None: base model)
+    # prompt-lookup decoding (None when off): verify steps the row was active in, and the accepted
+    # draft tokens among its output (len(tokens) == 1 + lookup_steps + lookup_accepted)
+    lookup_steps: Optional[int] = None
+    lookup_accepted: Optional[int] = None
 
 
 class ContinuousBatcher:
@@ -803,21 +864,48 @@ class ContinuousBatcher:
     without a seed gets ``derive_seed(params.seed, admission count)``; ``FinishedRow.seed`` reports
     it. With ``per_request=False`` graph keys and the RNG stream are the scalar sampler's.
 
+    ``lookup_tokens=K`` (1..7; ``lookup_ngram``): prompt-lookup speculative decoding. The replayed
+    step is the verify step (``Generator._step_verify``) over K + 1 positions per row, so
+    ``max_batch * (K + 1)`` must fit the fused decode layer (16 rows under MXFP4 decode) and a
+    prompt needs room for K more cache slots. An admission writes its rows' token history and first
+    draft only; a row emits 1 .. K + 1 tokens per step, and ``FinishedRow.lookup_steps`` /
+    ``lookup_accepted`` report its verify steps and accepted draft tokens. Greedy answers are the
+    plain batcher's. With ``per_request`` the sampler draws position j of a row with the counter of
+    output index ``gen_len + j``: a sampled answer is the plain per-request answer for the same
+    seed, and ``RequestSampling.lookup_tokens`` (0..K) gives a request its own draft length.
+    Not with adapters. ``SamplingParams.lookup_tokens`` stays refused here (it selects lookup for
+    ``Generator.generate``); with ``lookup_tokens=0`` nothing differs from a batcher without it.
+
     Usage: ``admit(prompt_ids, tag)`` while ``free_rows()``; ``step(n)``; ``collect()`` returns the
     rows that finished (a host read of the per-row flags once per call)."""
 
     def __init__(self, gen: Generator, params: SamplingParams, pad_id: int = 0, eos_ids: Sequence[int] = (),
-                 per_request: bool = False, adapters=None):
+                 per_request: bool = False, adapters=None, lookup_tokens: int = 0, lookup_ngram: int = 2):
         if adapters is not None:
             _check_bank(gen, params, adapters)
         if params.lookup_tokens > 0:
-            raise NotImplementedError("prompt-lookup decoding is not supported with continuous batching")
+            raise NotImplementedError("prompt-lookup decoding in the continuous batch is selected by the batcher's own "
+                                      "keyword, ContinuousBatcher(..., lookup_tokens=K, lookup_ngram=n), not by "
+                                      "SamplingParams.lookup_tokens")
         if _fp4_decode_on(gen.model) and gen.max_batch > 16:
             raise ValueError(f"continuous batching with MXFP4 decode (model.fp4_decode): max_batch {gen.max_batch} "
                              f"exceeds the 16 rows of the MXFP4 decode kernels")
+        K = int(lookup_tokens)
+        # the parameters the generator's step runs under: the caller's, plus the batcher's lookup setting
+        self.vparams = params
+        if K != 0:
+            import dataclasses
+
+            self.vparams = dataclasses.replace(params, lookup_tokens=K, lookup_ngram=int(lookup_ngram))
+            gen._check_lookup(self.vparams)
+            if adapters is not None:
+                raise ValueError("per-request adapters: prompt-lookup decoding (lookup_tokens > 0) is not supported")
+            gen._check_verify_rows(gen.max_batch, K)
+        self.K = K
         self.gen, self.params, self.pad_id = gen, params, pad_id
         g = gen
         g._lk = None
+        g._lk_rows = False
         dev, MB, T = g.device, g.max_batch, params.max_new_tokens
         self.T = T
         self.eos_list = list(eos_ids) or [g.cfg.eos_token_id]
@@ -841,6 +929,21 @@ class ContinuousBatcher:
         if self.per_request:
             # every row starts at the batcher's defaults (the capture below runs the step on them)
             g._row_buffers().write(0, [RequestSampling().resolve(params, T, 0)] * MB)
+        self.lookup_totals = None  # (row-steps, drafted, accepted) of the device counters, read in collect()
+        if K > 0:
+            # history and the verify step's buffers exist before the capture; no row is active, so the
+            # captured step's sampler and bookkeeping are masked everywhere
+            st = g._lk = g._lookup_buffers(K)
+            g._lk_rows = True
+            for t in (st.counters, st.row_stats, st.n_draft, st.row_active):
+                t.zero_()
+            st.inp.fill_(pad_id)
+            # the verify attention's row invariant (slot = keys - 1 >= 0) also for never-admitted rows
+            g.attn_len.fill_(1)
+            g.pos.zero_()
+            if self.per_request:
+                g.rowp.draft_buffer(K)
+            self.lookup_totals = (0, 0, 0)
         self._prev_merged = g.model.set_lora_merged(g.merge_lora) if hasattr(g.model, "set_lora_merged") else None
         self.adapters = adapters
         self.row_adapter = {}  # row -> adapter name
@@ -851,9 +954,9 @@ class ContinuousBatcher:
             g.adapter_ids.fill_(-1)
             adapters.refresh()
         if hasattr(g.model, "refresh_decode_weights"):
-            g.model.refresh_decode_weights(MB)
+            g.model.refresh_decode_weights(MB * (K + 1))  # a verify step runs K + 1 positions per row
         if T > 1:
-            g._ensure_graph(params, self.eos, self.eos_list, pad_id, T)  # captured while no row is active
+            g._ensure_graph(self.vparams, self.eos, self.eos_list, pad_id, T)  # captured while no row is active
         self.rows = {}  # row -> (tag, prompt_len, steps at admission)
         self.free = list(range(MB))
         self.steps = 0
@@ -861,6 +964,9 @@ class ContinuousBatcher:
     def close(self):
         self.gen._rows_on = False
         self.gen.adapters = None
+        if self.K > 0:
+            self.gen._lk = None
+            self.gen._lk_rows = False
         if self._prev_merged is not None:
             self.gen.model.set_lora_merged(self._prev_merged)
             self._prev_merged = None
@@ -898,20 +1004,27 @@ class ContinuousBatcher:
             raise ValueError("per-request sampling settings need ContinuousBatcher(per_request=True)")
         if len(prompts) > len(self.free):
             raise ValueError(f"{len(prompts)} requests for {len(self.free)} free rows")
-        resolved = None
+        resolved = drafts = None
         if self.per_request:
             # validated before any row is taken; unseeded requests are numbered by admission
+            for s in sampling:
+                if s is not None:
+                    s.validate(self.T, self.K)
             resolved = [(s or RequestSampling()).resolve(self.params, self.T, derive_seed(self.params.seed,
                                                                                          self.admitted + i))
                         for i, s in enumerate(sampling)]
+            if self.K > 0:
+                drafts = [self.K if s is None or s.lookup_tokens is None else s.lookup_tokens for s in sampling]
         for p in prompts:
-            if len(p) < 1 or len(p) + self.T > g.max_seq:
-                raise ValueError(f"prompt of {len(p)} tokens + {self.T} new exceeds the cache ({g.max_seq})")
+            # the last verify step may append K rows past the last emitted token
+            if len(p) < 1 or len(p) + self.T + self.K > g.max_seq:
+                raise ValueError(f"prompt of {len(p)} tokens + {self.T} new" + (f" + {self.K} draft" if self.K else "") +
+                                 f" exceeds the cache ({g.max_seq})")
         self.free.sort()
         rows, self.free = self.free[:len(prompts)], self.free[len(prompts):]
         try:
             if slots is None:
-                self._admit_runs(rows, prompts, tags, resolved)
+                self._admit_runs(rows, prompts, tags, resolved, drafts)
             else:
                 self._admit_adapter_runs(rows, prompts, tags, resolved, adapters, slots)
         except BaseException:
@@ -944,7 +1057,7 @@ class ContinuousBatcher:
                 self.row_adapter[rows[r]] = names[r]
             i = j
 
-    def _admit_runs(self, rows, prompts, tags, resolved=None):
+    def _admit_runs(self, rows, prompts, tags, resolved=None, drafts=None):
         g = self.gen
         i = 0
         while i < len(rows):
@@ -960,14 +1073,25 @@ class ContinuousBatcher:
                 ids[r, S - len(p):] = torch.tensor(p, dtype=torch.long)
                 start[r] = S - len(p)
             g.kv_start[b0:b0 + n].copy_(start.to(g.device, non_blocking=True))
-            h_last = g.model.prefill(ids.to(g.device, non_blocking=True), g.kv_start[b0:b0 + n],
-                                     _RowCache(g.cache, b0, n))
+            ids = ids.to(g.device, non_blocking=True)
+            h_last = g.model.prefill(ids, g.kv_start[b0:b0 + n], _RowCache(g.cache, b0, n))
             g.kv_len[b0:b0 + n].fill_(S - 1)  # the first bookkeeping advances them to S
             g.gen_len[b0:b0 + n].zero_()
             g.active[b0:b0 + n].fill_(1)
             if resolved is not None:
                 g.rowp.write(b0, resolved[i:j])
             g._emit(h_last, self.params, self.eos, self.pad_id, r0=b0)
+            if self.K > 0:
+                # what _enqueue does for a static batch, for these rows alone: history = the left-padded
+                # prompt, then the first sampled token at slot S (= kv_len, where the first verify step
+                # appends it), and the first draft. Slots past S hold the previous occupant's tokens,
+                # which the drafter never reads (it searches [kv_start, kv_len]).
+                g.hist[b0:b0 + n, :S] = ids
+                g.hist[b0:b0 + n, S] = g.tok_in[b0:b0 + n]
+                g._lk.row_stats[b0:b0 + n].zero_()
+                if drafts is not None:
+                    g.rowp.row_draft[b0:b0 + n].copy_(torch.tensor(drafts[i:j], dtype=torch.int32))
+                g._draft(self.vparams, self.pad_id, b0, b0 + n)
             for r in range(n):
                 self.rows[b0 + r] = (tags[i + r], len(grp[r]), self.steps)
                 if resolved is not None:
@@ -982,9 +1106,9 @@ class ContinuousBatcher:
         if nb != g._nb:
             g._nb = nb
             if self.T > 1:
-                g._ensure_graph(self.params, self.eos, self.eos_list, self.pad_id, self.T)
+                g._ensure_graph(self.vparams, self.eos, self.eos_list, self.pad_id, self.T)
         for _ in range(n):
-            g._replay(self.params, self.eos, self.pad_id)
+            g._replay(self.vparams, self.eos, self.pad_id)
         self.steps += n
 
     def collect(self) -> List[FinishedRow]:
@@ -1000,9 +1124,14 @@ class ContinuousBatcher:
             lens = g.gen_len.index_select(0, idx).cpu().tolist()
             toks = g.out_tokens.index_select(0, idx).cpu()
             lps = g.out_logp.index_select(0, idx).cpu()
-            for b, n, t, lp in zip(done, lens, toks, lps):
+            stats = [(None, None)] * len(done)
+            if self.K > 0:
+                # the stream is already drained by the reads above: two more small copies, no new wait
+                stats = g._lk.row_stats.index_select(0, idx).cpu().tolist()
+                self.lookup_totals = tuple(int(c) for c in g._lk.counters.tolist())
+            for b, n, t, lp, (ls, la) in zip(done, lens, toks, lps, stats):
                 tag, S, s0 = self.rows.pop(b)
                 out.append(FinishedRow(tag, t[:n].tolist(), lp[:n].tolist(), S, self.steps - s0,
-                                       self.row_seed.pop(b, None), self.row_adapter.pop(b, None)))
+                                       self.row_seed.pop(b, None), self.row_adapter.pop(b, None), ls, la))
                 self.free.append(b)
         return out

@@ -150,15 +150,20 @@ def sample(logits, inv_temp=1.0, top_k=0, top_p=1.0, greedy=False, seed=0, offse
     return out_tok, out_logp
 
 
-def sample_rows(logits, inv_temp, top_k, top_p, greedy, seed, counter, active=None, out_tok=None, out_logp=None):
+def sample_rows(logits, inv_temp, top_k, top_p, greedy, seed, counter, active=None, out_tok=None, out_logp=None,
+                group: int = 1):
     """``sample`` with per-row parameters, every one a [B] tensor on the logits' device: inv_temp
     f32, top_k i32 (0 = off), top_p f32, greedy u8, seed i64, counter i32. On the GPU the kernels
     read them from memory (a captured graph sees new values on replay) and row b draws from the
     Philox stream (seed[b], counter[b]) — what ``sample`` draws for that row alone with
-    ``seed = seed[b]`` and ``offset = [counter[b]]``. Returns (tokens int64 [B], logp [B])."""
+    ``seed = seed[b]`` and ``offset = [counter[b]]``. Returns (tokens int64 [B], logp [B]).
+
+    ``group`` = G > 1 (the verify step of prompt-lookup decoding): logits [B * G, V], G consecutive
+    rows per request; row r reads the parameters of request r // G and draws with the counter
+    ``counter[r // G] + r % G``. ``active`` and the outputs are [B * G]."""
     B = logits.shape[0]
     if not on_gpu(logits):
-        tok, lp = ref.sample_rows(logits, inv_temp, top_k, top_p, greedy, seed, counter, active)
+        tok, lp = ref.sample_rows(logits, inv_temp, top_k, top_p, greedy, seed, counter, active, group)
         if out_tok is not None:
             out_tok.copy_(tok)
             tok = out_tok
@@ -170,35 +175,48 @@ def sample_rows(logits, inv_temp, top_k, top_p, greedy, seed, counter, active=No
         out_tok = torch.empty(B, dtype=torch.long, device=logits.device)
     if out_logp is None:
         out_logp = torch.empty(B, dtype=torch.float32, device=logits.device)
-    native().sample_rows(logits, inv_temp, top_k, top_p, greedy, seed, counter, active, out_tok, out_logp)
+    if group == 1:
+        native().sample_rows(logits, inv_temp, top_k, top_p, greedy, seed, counter, active, out_tok, out_logp)
+    else:
+        native().sample_rows(logits, inv_temp, top_k, top_p, greedy, seed, counter, active, out_tok, out_logp, group)
     return out_tok, out_logp
 
 
 # ------------------------------------------------- prompt-lookup speculative decoding bookkeeping
 def lookup_accept(sampled, logp, inp, n_draft, out_tokens, out_logp, hist, active, kv_len, pos, attn_len, kv_start,
-                  gen_len, step, rng_offset, counters, eos_ids):
+                  gen_len, step, rng_offset, counters, eos_ids, row_max_new=None, row_stats=None):
     """Bookkeeping of a verify step, in place (``lookup_accept_kernel``): per active row accept the
     longest draft prefix ``inp[b, 1:]`` the sampler reproduced in ``sampled`` [B, G], emit
     ``sampled[b, :a + 1]`` (cut after the first EOS and at the output width) with its log-probs at
     the row's output position and into ``hist`` [B, Smax], advance the row's lengths.
-    ``counters`` int64 [3]: row-steps, drafted tokens, accepted-and-emitted tokens."""
+    ``counters`` int64 [3]: row-steps, drafted tokens, accepted-and-emitted tokens.
+    ``row_max_new`` int32 [B] (optional): the row's own answer length, it finishes at
+    ``min(row_max_new[b], T)``. ``row_stats`` int32 [B, 2] (optional): per row, the verify steps it
+    was active in and its accepted-and-emitted tokens are added."""
     args = (sampled, logp, inp, n_draft, out_tokens, out_logp, hist, active, kv_len, pos, attn_len, kv_start,
             gen_len, step, rng_offset, counters, eos_ids)
+    if row_max_new is not None or row_stats is not None:
+        args = args + (row_max_new, row_stats)
     if on_gpu(inp):
         native().lookup_accept(*args)
     else:
         ref.lookup_accept(*args)
 
 
-def lookup_draft(hist, kv_len, kv_start, active, ngram, pad_id, inp, n_draft, row_active):
+def lookup_draft(hist, kv_len, kv_start, active, ngram, pad_id, inp, n_draft, row_active, row_draft=None):
     """The next verify step's inputs, in place (``lookup_draft_kernel``): ``inp[b, 0]`` = the last
     emitted token ``hist[b, kv_len[b]]``, ``inp[b, 1:]`` = the tokens that followed the latest earlier
     occurrence of the row's last n-gram (n = ``ngram`` .. 1, starts in ``[kv_start, end - n)``),
-    ``n_draft[b]`` of them real and the rest pad; ``row_active`` [B*G] = the row's flag per position."""
+    ``n_draft[b]`` of them real and the rest pad; ``row_active`` [B*G] = the row's flag per position.
+    ``row_draft`` int32 [B] (optional): the row's own draft length, at most ``min(row_draft[b], G - 1)``
+    tokens are proposed (0: an empty draft)."""
+    args = (hist, kv_len, kv_start, active, ngram, pad_id, inp, n_draft, row_active)
+    if row_draft is not None:
+        args = args + (row_draft,)
     if on_gpu(inp):
-        native().lookup_draft(hist, kv_len, kv_start, active, ngram, pad_id, inp, n_draft, row_active)
+        native().lookup_draft(*args)
     else:
-        ref.lookup_draft(hist, kv_len, kv_start, active, ngram, pad_id, inp, n_draft, row_active)
+        ref.lookup_draft(*args)
 
 
 # ------------------------------------------------------------------------------- retrieval

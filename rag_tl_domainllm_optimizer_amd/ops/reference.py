@@ -206,10 +206,19 @@ def sample(logits, inv_temp=1.0, top_k=0, top_p=1.0, greedy=False, generator=Non
     return tok, x.gather(1, tok[:, None])[:, 0] - lse
 
 
-def sample_rows(logits, inv_temp, top_k, top_p, greedy, seed, counter, active=None):
+def sample_rows(logits, inv_temp, top_k, top_p, greedy, seed, counter, active=None, group=1):
     """Per-row parameters ([B] each): row b is filtered by ``filter_logits`` with its own settings
     and drawn from a generator seeded from (seed[b], counter[b]) alone, so the draw does not depend
-    on the row's place or its batch mates. Greedy and inactive rows return the argmax."""
+    on the row's place or its batch mates. Greedy and inactive rows return the argmax.
+    ``group`` = G > 1: logits [B * G, V]; row r takes the parameters of request r // G and the
+    counter counter[r // G] + r % G (``active`` is per logits row)."""
+    if group != 1:
+        if group < 1 or logits.shape[0] % group:
+            raise ValueError(f"sample_rows: group {group} must divide the {logits.shape[0]} logits rows")
+        rep = lambda t: t.repeat_interleave(group)  # noqa: E731
+        j = torch.arange(group, device=counter.device, dtype=counter.dtype).repeat(counter.shape[0])
+        return sample_rows(logits, rep(inv_temp), rep(top_k), rep(top_p), rep(greedy), rep(seed), rep(counter) + j,
+                           active)
     x = logits.float() * inv_temp.float()[:, None]
     lse = torch.logsumexp(x, -1)
     tok = x.argmax(-1)
@@ -355,7 +364,7 @@ def verify_attention(q, kc, vc, attn_len0, Hq, G, kv_start=None, window=0, scale
 
 
 def lookup_accept(sampled, logp, inp, n_draft, out_tokens, out_logp, hist, active, kv_len, pos, attn_len, kv_start,
-                  gen_len, step, rng_offset, counters, eos_ids):
+                  gen_len, step, rng_offset, counters, eos_ids, row_max_new=None, row_stats=None):
     """Twin of lookup_accept_kernel (in place). sampled / logp / inp [B, G]; see csrc/kernels/rl.hip."""
     B, G = inp.shape
     T, Smax = out_tokens.shape[1], hist.shape[1]
@@ -364,6 +373,7 @@ def lookup_accept(sampled, logp, inp, n_draft, out_tokens, out_logp, hist, activ
     for b in range(B):
         gl, kl = int(gen_len[b]), int(kv_len[b])
         if int(active[b]) != 0 and gl < T:
+            lim = min(int(row_max_new[b]), T) if row_max_new is not None else T
             nd = min(max(int(n_draft[b]), 0), G - 1)
             a = 0
             while a < nd and int(sm[b, a]) == int(inp[b, a + 1]):
@@ -376,7 +386,7 @@ def lookup_accept(sampled, logp, inp, n_draft, out_tokens, out_logp, hist, activ
                 if kl + 1 + i < Smax:
                     hist[b, kl + 1 + i] = t
                 e = i + 1
-                fin = gl + e >= T or t in eos
+                fin = gl + e >= lim or t in eos
                 if fin:
                     break
             gen_len[b] = gl + e
@@ -386,15 +396,18 @@ def lookup_accept(sampled, logp, inp, n_draft, out_tokens, out_logp, hist, activ
             counters[0] += 1
             counters[1] += nd
             counters[2] += e - 1
+            if row_stats is not None:
+                row_stats[b, 0] += 1
+                row_stats[b, 1] += e - 1
         attn_len[b] = int(kv_len[b]) + 1
         pos[b] = int(kv_len[b]) - int(kv_start[b])
     step += 1
     rng_offset += 1
 
 
-def lookup_draft(hist, kv_len, kv_start, active, ngram, pad_id, inp, n_draft, row_active):
+def lookup_draft(hist, kv_len, kv_start, active, ngram, pad_id, inp, n_draft, row_active, row_draft=None):
     """Twin of lookup_draft_kernel (in place): inp [B, G] = last emitted token | draft, n_draft [B],
-    row_active [B*G]."""
+    row_active [B*G]; row_draft [B] (optional) caps the row's draft at min(row_draft[b], G - 1)."""
     B, G = inp.shape
     Smax = hist.shape[1]
     ra = row_active.reshape(-1)
@@ -419,7 +432,8 @@ def lookup_draft(hist, kv_len, kv_start, active, ngram, pad_id, inp, n_draft, ro
             if best >= 0:
                 break
         cont = best + bn
-        avail = min(G - 1, end - cont) if best >= 0 else 0
+        cap = min(max(int(row_draft[b]), 0), G - 1) if row_draft is not None else G - 1
+        avail = min(cap, end - cont) if best >= 0 else 0
         inp[b, 0] = h[kl]
         for j in range(1, G):
             inp[b, j] = h[cont + j - 1] if j - 1 < avail else pad_id

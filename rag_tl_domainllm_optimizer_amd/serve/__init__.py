@@ -3,7 +3,9 @@ installed; FastAPI + uvicorn are). POST /answer {"query": "...", "top_k": 3} ->
 {"answer", "doc_ids", "docs", "scores", "timings"}; GET /health; GET /stats.
 With ``per_request_sampling`` (config ``serve.per_request_sampling``, continuous batching only) the
 body may also carry ``temperature``, ``top_k_tokens``, ``top_p``, ``do_sample``, ``seed`` and
-``max_new_tokens``; ``timings["seed"]`` returns the seed the answer was drawn with.
+``max_new_tokens``; ``timings["seed"]`` returns the seed the answer was drawn with. On a server
+with prompt-lookup decoding (``serve --eval.lookup_tokens=3``; GET /health reports ``lookup_tokens``)
+the body may also carry ``lookup_tokens`` in 0..K, the request's own draft length.
 
 Concurrent requests are batched: the async handler awaits a future while one worker thread owns the
 GPU — by default ``serve.continuous.ContinuousEngine`` (requests join the running decode batch
@@ -16,21 +18,23 @@ from .batching import BatchingEngine  # noqa: F401
 from .continuous import ContinuousEngine  # noqa: F401
 
 
-SAMPLING_FIELDS = ("temperature", "top_k_tokens", "top_p", "do_sample", "seed", "max_new_tokens")
+SAMPLING_FIELDS = ("temperature", "top_k_tokens", "top_p", "do_sample", "seed", "max_new_tokens", "lookup_tokens")
 
 
-def request_sampling(q, max_new_tokens: Optional[int] = None):
+def request_sampling(q, max_new_tokens: Optional[int] = None, lookup_tokens: Optional[int] = None):
     """The ``RequestSampling`` of an /answer body (None when it sets no sampling field); ValueError
     for a value outside its range. ``top_k`` stays the document count: the token top-k is
-    ``top_k_tokens``."""
+    ``top_k_tokens``. ``lookup_tokens``: the engine's draft length K (0: lookup off; None: the
+    body's value is only checked against 0..7)."""
     from ..generation import RequestSampling
 
     vals = {f: getattr(q, f, None) for f in SAMPLING_FIELDS}
     if all(v is None for v in vals.values()):
         return None
     rs = RequestSampling(temperature=vals["temperature"], top_k=vals["top_k_tokens"], top_p=vals["top_p"],
-                         do_sample=vals["do_sample"], seed=vals["seed"], max_new_tokens=vals["max_new_tokens"])
-    rs.validate(max_new_tokens)
+                         do_sample=vals["do_sample"], seed=vals["seed"], max_new_tokens=vals["max_new_tokens"],
+                         lookup_tokens=vals["lookup_tokens"])
+    rs.validate(max_new_tokens, lookup_tokens)
     return rs
 
 
@@ -49,6 +53,7 @@ def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, pe
         BatchingEngine(pipeline, max_wait_s=max_wait_s)
     app = FastAPI(title="rag-tl-domainllm-optimizer-amd")
     app.state.engine = engine
+    engine_k = getattr(engine, "lookup_tokens", 0) if continuous else 0  # the verify steps' draft length
 
     class Query(BaseModel):
         query: str
@@ -59,13 +64,14 @@ def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, pe
         do_sample: Optional[bool] = None
         seed: Optional[int] = None
         max_new_tokens: Optional[int] = None
+        lookup_tokens: Optional[int] = None  # draft tokens per step, 0 .. the server's eval.lookup_tokens
         adapter: Optional[str] = None  # a loaded LoRA adapter (servers with serve.adapters); None: the base model
 
     @app.get("/health")
     def health():
         return {"status": "ok", "docs": len(pipeline.docs), "max_batch": pipeline.max_batch,
                 "batching": "continuous" if continuous else "dynamic", "per_request_sampling": per_request_sampling,
-                "adapters": adapters.loaded() if adapters is not None else []}
+                "adapters": adapters.loaded() if adapters is not None else [], "lookup_tokens": engine_k}
 
     @app.get("/stats")
     def stats():
@@ -74,7 +80,8 @@ def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, pe
     @app.post("/answer")
     async def answer(q: Query):
         try:
-            rs = request_sampling(q, getattr(getattr(pipeline, "sampling", None), "max_new_tokens", None))
+            rs = request_sampling(q, getattr(getattr(pipeline, "sampling", None), "max_new_tokens", None),
+                                  engine_k if per_request_sampling else None)
         except ValueError as e:
             raise HTTPException(status_code=422, detail=str(e))
         if rs is not None and not per_request_sampling:
@@ -112,7 +119,8 @@ def serve(cfg, host: str = "127.0.0.1", port: int = 8000, max_batch: int = 16, m
     st = build_stack(cfg, di.device)
     apply_fp4(cfg, st["policy"])
     sp = SamplingParams(max_new_tokens=cfg.ppo.max_new_tokens, temperature=cfg.eval.temperature,
-                        do_sample=cfg.eval.do_sample, top_k=cfg.eval.top_k)
+                        do_sample=cfg.eval.do_sample, top_k=cfg.eval.top_k, lookup_tokens=cfg.eval.lookup_tokens,
+                        lookup_ngram=cfg.eval.lookup_ngram)
     rag = RagPipeline(st["encoder"], st["index"], st["docs"], st["policy"], st["tokenizer"], cfg.retrieval.top_k, sp,
                       cfg.ppo.max_prompt_tokens, max_batch=max_batch)
     if per_request_sampling is None:

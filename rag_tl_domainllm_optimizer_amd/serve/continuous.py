@@ -19,6 +19,14 @@ with, so a client can ask for the same answer again.
 ``adapters=bank`` (``models.AdapterBank``): ``submit(..., adapter="name")`` answers with that loaded
 LoRA adapter over the shared base weights, beside rows of other adapters or of the base model
 (``ContinuousBatcher(adapters=bank)``, at most 16 rows); ``timings["adapter"]`` reports it.
+
+Prompt-lookup decoding: a pipeline whose ``sampling.lookup_tokens`` is K > 0 (``serve
+--eval.lookup_tokens=3``) runs the batch on verify steps (``ContinuousBatcher(lookup_tokens=K,
+lookup_ngram=n)``; the batcher's ``SamplingParams`` carry ``lookup_tokens=0``). An answer's
+``timings`` gain ``lookup_steps`` (verify steps the row was active in) and ``lookup_accepted`` (its
+accepted draft tokens); ``stats`` keeps the running totals ``lookup_steps`` / ``lookup_drafted`` /
+``lookup_accepted`` over all rows. With ``per_request_sampling`` a request may bring its own
+``RequestSampling.lookup_tokens`` in 0..K. Not together with adapters.
 """
 from __future__ import annotations
 
@@ -30,6 +38,8 @@ from typing import List, Optional
 
 import torch
 
+import dataclasses
+
 from ..generation import ContinuousBatcher, RequestSampling
 from ..rag.pipeline import RagAnswer
 from ..rag.prompt import extract_answer
@@ -37,8 +47,8 @@ from ..rag.prompt import extract_answer
 
 class ContinuousEngine:
     def __init__(self, pipeline, chunk: int = 4, per_request_sampling: bool = False, adapters=None):
-        if pipeline.sampling.lookup_tokens > 0:
-            raise NotImplementedError("prompt-lookup decoding is not supported with continuous batching")
+        self.lookup_tokens = int(pipeline.sampling.lookup_tokens)
+        self.lookup_ngram = int(getattr(pipeline.sampling, "lookup_ngram", 2))
         layers = getattr(pipeline.gen.model, "layers", None)
         if layers and getattr(layers[0], "fp4_decode", False) and pipeline.max_batch > 16:
             raise ValueError(f"continuous batching with MXFP4 decode (model.fp4_decode): max_batch {pipeline.max_batch} "
@@ -52,6 +62,8 @@ class ContinuousEngine:
         self._dead: Optional[BaseException] = None  # the error that ended the worker, if any
         self._lock = threading.Lock()  # submit's closed-check + put vs the worker's final drain
         self.stats = {"admitted": 0, "finished": 0, "steps": 0, "max_active": 0}
+        if self.lookup_tokens > 0:
+            self.stats.update({"lookup_steps": 0, "lookup_drafted": 0, "lookup_accepted": 0})
         self._row_steps = 0  # sum over decode steps of the active rows (an answer's mean batch)
         self._ready = threading.Event()
         self._init_error = None
@@ -71,7 +83,7 @@ class ContinuousEngine:
         if sampling is not None:
             if not self.per_request_sampling:
                 raise ValueError("per-request sampling settings need ContinuousEngine(per_request_sampling=True)")
-            sampling.validate(self.pipeline.sampling.max_new_tokens)
+            sampling.validate(self.pipeline.sampling.max_new_tokens, self.lookup_tokens)
         with self._lock:
             if self._closed:
                 if self._dead is not None:
@@ -127,7 +139,7 @@ class ContinuousEngine:
         for it, row_ids, row_sc in zip(live, ids_l, sc_l):
             docs = [p.docs[i] for i in row_ids if i >= 0]
             prompt = p._prompt_ids(it[0], docs)
-            if len(prompt) + cb.T > p.gen.max_seq:
+            if len(prompt) + cb.T + cb.K > p.gen.max_seq:
                 it[2].set_exception(ValueError("prompt does not fit the serving cache"))
                 continue
             prompts.append(prompt)
@@ -166,14 +178,23 @@ class ContinuousEngine:
                 tim["seed"] = r.seed
             if self.adapters is not None:
                 tim["adapter"] = r.adapter
+            if r.lookup_steps is not None:
+                tim["lookup_steps"], tim["lookup_accepted"] = r.lookup_steps, r.lookup_accepted
             m["fut"].set_result(RagAnswer(m["query"], text, m["doc_ids"], m["docs"], m["scores"], tim))
             self.stats["finished"] += 1
 
     def _loop(self):
         p = self.pipeline
         try:
-            cb = ContinuousBatcher(p.gen, p.sampling, pad_id=p.tok.pad_token_id, eos_ids=[p.tok.eos_token_id],
-                                   per_request=self.per_request_sampling, adapters=self.adapters)
+            if self.lookup_tokens > 0:
+                # the batcher takes lookup as its own keyword; its SamplingParams carry none
+                cb = ContinuousBatcher(p.gen, dataclasses.replace(p.sampling, lookup_tokens=0),
+                                       pad_id=p.tok.pad_token_id, eos_ids=[p.tok.eos_token_id],
+                                       per_request=self.per_request_sampling, adapters=self.adapters,
+                                       lookup_tokens=self.lookup_tokens, lookup_ngram=self.lookup_ngram)
+            else:
+                cb = ContinuousBatcher(p.gen, p.sampling, pad_id=p.tok.pad_token_id, eos_ids=[p.tok.eos_token_id],
+                                       per_request=self.per_request_sampling, adapters=self.adapters)
         except BaseException as e:  # noqa: BLE001
             self._init_error = e
             self._ready.set()
@@ -205,7 +226,11 @@ class ContinuousEngine:
                     self._row_steps += cb.active_rows() * self.chunk
                     cb.step(self.chunk)
                     self.stats["steps"] += self.chunk
-                    self._finish(cb.collect())
+                    done = cb.collect()
+                    if cb.lookup_totals is not None:
+                        (self.stats["lookup_steps"], self.stats["lookup_drafted"],
+                         self.stats["lookup_accepted"]) = cb.lookup_totals
+                    self._finish(done)
         except BaseException as e:  # noqa: BLE001 - in-flight callers get the error
             self._dead = e
             for b, (meta, _, _) in list(cb.rows.items()):
