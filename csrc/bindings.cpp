@@ -111,6 +111,10 @@ int rt_lookup_accept(const long*, const float*, const long*, const int*, int, lo
                      const int*, int*, hipStream_t);
 int rt_lookup_draft(const long*, int, const int*, const int*, const uint8_t*, int, int, long, long*, int*, uint8_t*, int,
                     const int*, hipStream_t);
+int rt_logit_rows_max_seq();
+int rt_logit_rows_penalty(void*, int, long, long, int, long*, int, const long*, const int*, const int*, const int*,
+                          const uint8_t*, const float*, const float*, const float*, const float*, const int*, const int*,
+                          const float*, hipStream_t);
 }
 
 namespace {
@@ -1689,6 +1693,46 @@ void lookup_draft(const Tensor& hist, const Tensor& kv_len, const Tensor& kv_sta
            "lookup_draft");
 }
 
+// Per-request logit penalties, in place on the logits rows and (tok_in given) on the rows' history:
+// one workgroup per row, every parameter a per-row device buffer (logit_rows.hip).
+void logit_rows_penalty(Tensor logits, Tensor hist, const optional<Tensor>& tok_in, const Tensor& kv_len,
+                        const Tensor& kv_start, const Tensor& gen_len, const optional<Tensor>& active, const Tensor& rho,
+                        const Tensor& inv_rho, const Tensor& pi, const Tensor& phi, const Tensor& nbias,
+                        const Tensor& bias_tok, const Tensor& bias_val) {
+  CHECK_CUDA(logits); CHECK_ROWS(logits); CHECK_CUDA(hist); CHECK_I64(hist);
+  TORCH_CHECK(logits.scalar_type() == at::kFloat || logits.scalar_type() == at::kBFloat16,
+              "logit_rows_penalty: logits must be float32 or bfloat16");
+  const int64_t B = logits.size(0);
+  TORCH_CHECK(hist.dim() == 2 && hist.is_contiguous() && hist.size(0) == B, "logit_rows_penalty: hist must be contiguous [B, S]");
+  TORCH_CHECK(hist.size(1) <= rt_logit_rows_max_seq(), "logit_rows_penalty: history of ", hist.size(1),
+              " slots exceeds the supported ", rt_logit_rows_max_seq());
+  CHECK_I32(kv_len); CHECK_I32(kv_start); CHECK_I32(gen_len); CHECK_F32(rho); CHECK_F32(inv_rho); CHECK_F32(pi);
+  CHECK_F32(phi); CHECK_I32(nbias); CHECK_I32(bias_tok); CHECK_F32(bias_val);
+  auto vec = [&](const Tensor& t, const char* name, int64_t n) {
+    TORCH_CHECK(t.is_cuda() && t.get_device() == logits.get_device(), "logit_rows_penalty: ", name,
+                " must be on the logits' device");
+    TORCH_CHECK(t.is_contiguous() && t.numel() == n, "logit_rows_penalty: ", name, " must be contiguous with ", n,
+                " elements");
+  };
+  vec(hist, "hist", B * hist.size(1));
+  vec(kv_len, "kv_len", B); vec(kv_start, "kv_start", B); vec(gen_len, "gen_len", B); vec(rho, "rho", B);
+  vec(inv_rho, "inv_rho", B); vec(pi, "pi", B); vec(phi, "phi", B); vec(nbias, "nbias", B);
+  vec(bias_tok, "bias_tok", B * 16); vec(bias_val, "bias_val", B * 16);
+  if (tok_in.has_value() && tok_in->defined()) { CHECK_I64(*tok_in); vec(*tok_in, "tok_in", B); }
+  if (active.has_value() && active->defined()) {
+    TORCH_CHECK(active->scalar_type() == at::kByte || active->scalar_type() == at::kBool, "active must be uint8 or bool");
+    vec(*active, "active", B);
+  }
+  check_rc(rt_logit_rows_penalty(logits.data_ptr(), logits.scalar_type() == at::kFloat, logits.stride(0), B,
+                                 (int)logits.size(1), (long*)hist.data_ptr(), (int)hist.size(1),
+                                 (const long*)opt_ptr(tok_in), kv_len.data_ptr<int>(), kv_start.data_ptr<int>(),
+                                 gen_len.data_ptr<int>(), (const uint8_t*)opt_ptr(active), rho.data_ptr<float>(),
+                                 inv_rho.data_ptr<float>(), pi.data_ptr<float>(), phi.data_ptr<float>(),
+                                 nbias.data_ptr<int>(), bias_tok.data_ptr<int>(), bias_val.data_ptr<float>(),
+                                 cur_stream()),
+           "logit_rows_penalty");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1803,6 +1847,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lookup_draft", &lookup_draft, "prompt-lookup decoding: next inputs = last token + n-gram draft",
         py::arg("hist"), py::arg("kv_len"), py::arg("kv_start"), py::arg("active"), py::arg("ngram"), py::arg("pad_id"),
         py::arg("inp"), py::arg("n_draft"), py::arg("row_active"), py::arg("row_draft") = py::none());
+  m.def("logit_rows_penalty", &logit_rows_penalty,
+        "per-request repetition / presence / frequency penalties and logit bias, in place on the logits rows",
+        py::arg("logits"), py::arg("hist"), py::arg("tok_in"), py::arg("kv_len"), py::arg("kv_start"), py::arg("gen_len"),
+        py::arg("active"), py::arg("rho"), py::arg("inv_rho"), py::arg("pi"), py::arg("phi"), py::arg("nbias"),
+        py::arg("bias_tok"), py::arg("bias_val"));
+  m.def("logit_rows_max_seq", []() { return rt_logit_rows_max_seq(); }, "history slots logit_rows_penalty supports");
   ragtl::bind_tokenizer(m);
   ragtl::bind_ivf_host(m);
 }

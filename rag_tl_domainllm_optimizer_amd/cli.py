@@ -412,13 +412,18 @@ def cmd_serve(cfg, args):
 
     if args.per_request_sampling is not None:
         cfg.serve.per_request_sampling = args.per_request_sampling
+    if args.logit_penalties is not None:
+        cfg.serve.logit_penalties = args.logit_penalties
+    if cfg.serve.logit_penalties and not cfg.serve.per_request_sampling:
+        raise SystemExit("serve: --logit-penalties (serve.logit_penalties) needs --per-request-sampling")
     adapters = {}
     for item in args.adapter or []:
         name, sep, path = item.partition("=")
         if not sep or not name or not path:
             raise SystemExit(f"serve: --adapter takes name=path, got {item!r}")
         adapters[name] = path
-    serve(cfg, host=args.host, port=args.port, per_request_sampling=cfg.serve.per_request_sampling, adapters=adapters)
+    serve(cfg, host=args.host, port=args.port, per_request_sampling=cfg.serve.per_request_sampling, adapters=adapters,
+          logit_penalties=cfg.serve.logit_penalties)
 
 
 def cmd_bench(cfg, args, rest):
@@ -453,6 +458,9 @@ def main(argv: Optional[List[str]] = None):
     ap.add_argument("--nproc", type=int, default=1)
     ap.add_argument("--per-request-sampling", dest="per_request_sampling", action=argparse.BooleanOptionalAction,
                     default=None, help="serve: accept per-request sampling settings (serve.per_request_sampling)")
+    ap.add_argument("--logit-penalties", dest="logit_penalties", action=argparse.BooleanOptionalAction, default=None,
+                    help="serve: accept per-request repetition / presence / frequency penalties and logit_bias "
+                         "(serve.logit_penalties; needs --per-request-sampling)")
     ap.add_argument("--adapter", action="append", default=[],
                     help="serve: name=path of a PEFT LoRA adapter a request may pick (repeatable; serve.adapters)")
     ap.add_argument("--env", action="append", default=[], help="launch: KEY=VALUE set for every rank (repeatable)")

@@ -69,6 +69,9 @@ class ServeSection:
     # requests may carry their own temperature / top-k / top-p / greedy flag / seed / answer length
     # (continuous batching; the sampled stream then differs from the one-configuration server's)
     per_request_sampling: bool = False
+    # requests may also carry repetition_penalty / presence_penalty / frequency_penalty / logit_bias
+    # (needs per_request_sampling; one more small launch per decode step; not with eval.lookup_tokens)
+    logit_penalties: bool = False
     # LoRA adapters resident over the served base model, name -> PEFT directory: a request picks one
     # with its "adapter" field (continuous batching, at most 16 rows); empty: one model, as before
     adapters: Dict[str, str] = field(default_factory=dict)

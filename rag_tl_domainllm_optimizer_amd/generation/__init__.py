@@ -36,6 +36,13 @@ class SamplingParams:
     # n-gram, n = lookup_ngram .. 1) and verified in one forward over K + 1 positions. 0: off
     lookup_tokens: int = 0
     lookup_ngram: int = 2
+    # logit penalties: the defaults of a ``ContinuousBatcher(penalties=True)``; neutral = off.
+    # repetition_penalty rho > 0 (HF semantics, prompt and generated tokens), presence / frequency
+    # penalty in [-2, 2] (OpenAI semantics, generated tokens), logit_bias {token: bias in [-100, 100]}
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logit_bias: Optional[object] = None
 
     @property
     def greedy(self) -> bool:
@@ -44,6 +51,52 @@ class SamplingParams:
     @property
     def inv_temp(self) -> float:
         return 1.0 if self.greedy else 1.0 / self.temperature
+
+
+MAX_LOGIT_BIAS = 16  # (token, bias) pairs per request
+
+
+def _bias_pairs(logit_bias):
+    """``logit_bias`` (None, a dict or a list of pairs) as a tuple of (token, bias) pairs; ValueError
+    for more than 16 pairs, a token that is no integer >= 0, a duplicate token, or a bias outside
+    [-100, 100]. Keys that are strings of digits (the OpenAI API's JSON object) are accepted."""
+    if logit_bias is None:
+        return ()
+    items = list(logit_bias.items()) if isinstance(logit_bias, dict) else [tuple(x) for x in logit_bias]
+    if len(items) > MAX_LOGIT_BIAS:
+        raise ValueError(f"logit_bias: {len(items)} entries, at most {MAX_LOGIT_BIAS} per request")
+    out, seen = [], set()
+    for it in items:
+        if len(it) != 2:
+            raise ValueError(f"logit_bias: entries are (token, bias) pairs, got {it!r}")
+        t, v = it
+        if isinstance(t, str) and t.strip().lstrip("+").isdigit():
+            t = int(t)
+        if isinstance(t, bool) or not isinstance(t, int) or t < 0:
+            raise ValueError(f"logit_bias: token {t!r} must be an integer >= 0")
+        if t in seen:
+            raise ValueError(f"logit_bias: token {t} given twice")
+        seen.add(t)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not -100 <= v <= 100:
+            raise ValueError(f"logit_bias[{t}] = {v!r}: must be in [-100, 100]")
+        out.append((t, float(v)))
+    return tuple(out)
+
+
+def _check_penalties(rho, pi, phi, logit_bias, vocab=None):
+    """Range checks of the four penalty settings (None: not set); returns the bias pairs."""
+    if rho is not None and not (rho > 0 and rho != float("inf")):
+        raise ValueError(f"repetition_penalty = {rho}: must be a finite number > 0 (1 = off)")
+    if pi is not None and not -2 <= pi <= 2:
+        raise ValueError(f"presence_penalty = {pi}: must be in [-2, 2] (0 = off)")
+    if phi is not None and not -2 <= phi <= 2:
+        raise ValueError(f"frequency_penalty = {phi}: must be in [-2, 2] (0 = off)")
+    pairs = _bias_pairs(logit_bias)
+    if vocab is not None:
+        for t, _ in pairs:
+            if t >= vocab:
+                raise ValueError(f"logit_bias: token {t} is outside the vocabulary [0, {vocab})")
+    return pairs
 
 
 _MIX = 0x9E3779B97F4A7C15  # 2**64 / golden ratio: spreads consecutive integers over 64 bits
@@ -71,10 +124,25 @@ class RequestSampling:
     # draft tokens per verify step of this request, 0 .. the batcher's lookup_tokens (None: the
     # batcher's); only for batchers with prompt-lookup decoding on
     lookup_tokens: Optional[int] = None
+    # logit penalties, only for batchers built with ``penalties=True`` (None: the batcher's
+    # ``SamplingParams`` value): repetition penalty rho > 0 (1 = off), presence / frequency penalty
+    # in [-2, 2] (0 = off), logit_bias = {token: bias in [-100, 100]} or a list of such pairs (<= 16)
+    repetition_penalty: Optional[float] = None
+    presence_penalty: Optional[float] = None
+    frequency_penalty: Optional[float] = None
+    logit_bias: Optional[object] = None
 
-    def validate(self, max_new: Optional[int] = None, lookup: Optional[int] = None):
+    @property
+    def has_penalties(self) -> bool:
+        """True when the request sets a penalty field (neutral values included)"""
+        return any(v is not None for v in (self.repetition_penalty, self.presence_penalty, self.frequency_penalty,
+                                           self.logit_bias))
+
+    def validate(self, max_new: Optional[int] = None, lookup: Optional[int] = None, vocab: Optional[int] = None):
         """ValueError for a setting outside its range (``max_new``: the batcher's output width;
-        ``lookup``: the batcher's draft length K, 0 = lookup off, None = not checked here)."""
+        ``lookup``: the batcher's draft length K, 0 = lookup off, None = not checked here; ``vocab``:
+        the vocabulary size bias tokens must lie in, None = not checked here)."""
+        _check_penalties(self.repetition_penalty, self.presence_penalty, self.frequency_penalty, self.logit_bias, vocab)
         if self.lookup_tokens is not None:
             if not (isinstance(self.lookup_tokens, int) and 0 <= self.lookup_tokens <= 7):
                 raise ValueError(f"lookup_tokens = {self.lookup_tokens}: must be an integer in [0, 7]")
@@ -107,6 +175,15 @@ class RequestSampling:
                 float(pick(self.top_p, params.top_p)), bool(greedy), int(pick(self.seed, default_seed)),
                 int(pick(self.max_new_tokens, max_new)))
 
+    def resolve_penalties(self, params: SamplingParams, vocab: Optional[int] = None):
+        """(rho, presence, frequency, ((token, bias), ...)) with the batcher's defaults filled in"""
+        pick = lambda v, d: d if v is None else v  # noqa: E731
+        rho = float(pick(self.repetition_penalty, params.repetition_penalty))
+        pi = float(pick(self.presence_penalty, params.presence_penalty))
+        phi = float(pick(self.frequency_penalty, params.frequency_penalty))
+        pairs = _check_penalties(rho, pi, phi, pick(self.logit_bias, params.logit_bias), vocab)
+        return rho, pi, phi, pairs
+
 
 class _RowParams:
     """Static per-row sampling parameters (device memory the captured decode step reads)."""
@@ -136,6 +213,48 @@ class _RowParams:
         """rows: ``RequestSampling.resolve`` tuples of rows b0.. (host-to-device copies, outside any graph)"""
         for t, col in zip(self.tensors(), zip(*rows)):
             t[b0:b0 + len(rows)].copy_(torch.tensor(col, dtype=t.dtype))
+
+
+class _RowPenalties:
+    """Static per-row logit-penalty parameters (device memory the captured decode step reads);
+    every row starts neutral."""
+
+    def __init__(self, B: int, device):
+        self.rho = torch.ones(B, dtype=torch.float32, device=device)
+        self.inv_rho = torch.ones(B, dtype=torch.float32, device=device)  # 1 / rho, rounded once on the host
+        self.pi = torch.zeros(B, dtype=torch.float32, device=device)
+        self.phi = torch.zeros(B, dtype=torch.float32, device=device)
+        self.nbias = torch.zeros(B, dtype=torch.int32, device=device)
+        self.bias_tok = torch.zeros(B, MAX_LOGIT_BIAS, dtype=torch.int32, device=device)
+        self.bias_val = torch.zeros(B, MAX_LOGIT_BIAS, dtype=torch.float32, device=device)
+
+    def tensors(self):
+        return [self.rho, self.inv_rho, self.pi, self.phi, self.nbias, self.bias_tok, self.bias_val]
+
+    def reset(self):
+        for t, v in zip(self.tensors(), (1, 1, 0, 0, 0, 0, 0)):
+            t.fill_(v)
+
+    def write(self, b0: int, rows):
+        """rows: ``RequestSampling.resolve_penalties`` tuples of rows b0.. (host-to-device copies,
+        outside any graph)"""
+        n = len(rows)
+        rho = torch.tensor([r[0] for r in rows], dtype=torch.float32)
+        tok = torch.zeros(n, MAX_LOGIT_BIAS, dtype=torch.int32)
+        val = torch.zeros(n, MAX_LOGIT_BIAS, dtype=torch.float32)
+        for i, r in enumerate(rows):
+            for j, (t, v) in enumerate(r[3]):
+                tok[i, j], val[i, j] = t, v
+        cols = (rho, 1.0 / rho, torch.tensor([r[1] for r in rows], dtype=torch.float32),
+                torch.tensor([r[2] for r in rows], dtype=torch.float32),
+                torch.tensor([len(r[3]) for r in rows], dtype=torch.int32), tok, val)
+        for t, col in zip(self.tensors(), cols):
+            t[b0:b0 + n].copy_(col)
+
+
+def _neutral_penalties(params: SamplingParams) -> bool:
+    return (params.repetition_penalty == 1.0 and params.presence_penalty == 0.0 and params.frequency_penalty == 0.0
+            and not params.logit_bias)
 
 
 @dataclass
@@ -282,6 +401,10 @@ class Generator:
         # per row (-1 = base model), written at admission outside any graph like the row parameters
         self.adapters = None
         self.adapter_ids = None
+        # per-request logit penalties (ContinuousBatcher(penalties=True)): per-row parameter buffers,
+        # allocated on first use; _pen_on puts ops.logit_rows_penalty in front of the per-row sampler
+        self.penp = None
+        self._pen_on = False
 
     # ------------------------------------------------------------------ one decode step (device only)
     def _bucket(self, B: int) -> int:
@@ -314,6 +437,14 @@ class Generator:
         if st is None:
             st = self._lookup[K] = _LookupState(self.max_batch, K + 1, self.device)
         return st
+
+    def _penalty_buffers(self) -> _RowPenalties:
+        """The penalty parameters and the token history the kernel scans (shared with lookup)"""
+        if self.penp is None:
+            self.penp = _RowPenalties(self.max_batch, self.device)
+        if self.hist is None:
+            self.hist = torch.zeros(self.max_batch, self.max_seq, dtype=torch.long, device=self.device)
+        return self.penp
 
     def _row_buffers(self) -> _RowParams:
         if self.rowp is None:
@@ -392,12 +523,21 @@ class Generator:
                          params.lookup_ngram, pad_id, st.inp[r0:r1], st.n_draft[r0:r1],
                          st.row_active[r0 * st.G:r1 * st.G], row_draft=rd)
 
-    def _emit(self, h, params: SamplingParams, eos_ids, pad_id, r0: int = 0):
+    def _emit(self, h, params: SamplingParams, eos_ids, pad_id, r0: int = 0, append: bool = True):
         """Sample from the hidden states of rows [r0, r0 + len(h)) and run the bookkeeping for them
-        (the decode step's row bucket, or one row admitted by continuous batching)."""
+        (the decode step's row bucket, or one row admitted by continuous batching). ``append``
+        (logit penalties only): the rows' input tokens join their history first — True for a decode
+        step, False for an admission's prefill logits (the history is the prompt alone)."""
         r1 = r0 + h.shape[0]
         logits = self.model.logits(h)
         rp = self.rowp if self._rows_on else None
+        if rp is not None and self._pen_on:
+            # the row's own penalties, in place, before its sampler reads the logits
+            pp = self.penp
+            ops.logit_rows_penalty(logits, self.hist[r0:r1], self.tok_in[r0:r1] if append else None,
+                                   self.kv_len[r0:r1], self.kv_start[r0:r1], self.gen_len[r0:r1], self.active[r0:r1],
+                                   pp.rho[r0:r1], pp.inv_rho[r0:r1], pp.pi[r0:r1], pp.phi[r0:r1], pp.nbias[r0:r1],
+                                   pp.bias_tok[r0:r1], pp.bias_val[r0:r1])
         if rp is not None:
             # the row's own settings and stream: (seed, tokens generated so far) key the draw
             ops.sample_rows(logits, rp.inv_temp[r0:r1], rp.top_k[r0:r1], rp.top_p[r0:r1], rp.greedy[r0:r1],
@@ -492,7 +632,12 @@ class Generator:
         if params.max_length is not None:
             T = max(1, min(T, params.max_length - S))
         self._check_lookup(params)
+        if not _neutral_penalties(params):
+            raise ValueError("logit penalties (repetition_penalty, presence_penalty, frequency_penalty, logit_bias) "
+                             "are served by ContinuousBatcher(per_request=True, penalties=True) only, not by "
+                             "Generator.generate")
         self._rows_on = False  # a batch under one SamplingParams: the scalar sampler and its stream
+        self._pen_on = False
         self._lk_rows = False
         K = params.lookup_tokens
         # the last verify step may append K rows past the last emitted token
@@ -595,6 +740,8 @@ class Generator:
             key = key + ("fp4",)  # the captured step of the other setting streams other weight images
         if self.adapters is not None:
             key = key + ("adapters",)  # slots are read from the row buffer: one graph per bucket whatever the mix
+        if self._pen_on:
+            key = key + ("penalties",)  # the step carries the penalty launch; settings are read from the row buffers
         if self._lk is not None:
             # a verify step is its own graph per (K, n-gram length); plain keys are unchanged
             key = key + ("lookup", params.lookup_tokens, params.lookup_ngram)
@@ -619,6 +766,8 @@ class Generator:
             st += [self.hist] + self._lk.tensors()
         if self.rowp is not None:
             st += self.rowp.tensors()
+        if self._pen_on:
+            st += [self.hist] + self.penp.tensors()
         return st
 
 
@@ -876,13 +1025,40 @@ class ContinuousBatcher:
     Not with adapters. ``SamplingParams.lookup_tokens`` stays refused here (it selects lookup for
     ``Generator.generate``); with ``lookup_tokens=0`` nothing differs from a batcher without it.
 
+    ``penalties=True`` (needs ``per_request``): a ``RequestSampling`` may also bring
+    ``repetition_penalty``, ``presence_penalty``, ``frequency_penalty`` and ``logit_bias`` (defaults:
+    the ``SamplingParams`` fields of the same names). ``ops.logit_rows_penalty`` rewrites the touched
+    logits of each row in place between the LM head and the sampler, inside the captured step and on
+    an admission's prefill logits, from per-row device buffers and the row's token history
+    (``Generator.hist``): one graph per bucket whatever the mix, the reported log-probs are those of
+    the penalised distribution, and a neutral row's tokens, log-probs and random stream are those
+    of a batcher without the flag. ``max_seq`` at most ``ops.LOGIT_ROWS_MAX_SEQ``; not together with
+    ``lookup_tokens``. With the flag off no buffer, graph key or launch differs.
+
     Usage: ``admit(prompt_ids, tag)`` while ``free_rows()``; ``step(n)``; ``collect()`` returns the
     rows that finished (a host read of the per-row flags once per call)."""
 
     def __init__(self, gen: Generator, params: SamplingParams, pad_id: int = 0, eos_ids: Sequence[int] = (),
-                 per_request: bool = False, adapters=None, lookup_tokens: int = 0, lookup_ngram: int = 2):
+                 per_request: bool = False, adapters=None, lookup_tokens: int = 0, lookup_ngram: int = 2,
+                 penalties: bool = False):
         if adapters is not None:
             _check_bank(gen, params, adapters)
+        self.penalties = bool(penalties)
+        if self.penalties:
+            if not per_request:
+                raise ValueError("logit penalties are per-request settings: ContinuousBatcher(penalties=True) needs "
+                                 "per_request=True")
+            if int(lookup_tokens) > 0:
+                raise ValueError("logit penalties with prompt-lookup decoding (lookup_tokens > 0) are not supported: "
+                                 "position j of a verify step would need the draft tokens before it in its history")
+            if gen.max_seq > ops.LOGIT_ROWS_MAX_SEQ:
+                raise ValueError(f"logit penalties: max_seq {gen.max_seq} exceeds the {ops.LOGIT_ROWS_MAX_SEQ} history "
+                                 f"slots the penalty kernel stages per row")
+            _check_penalties(params.repetition_penalty, params.presence_penalty, params.frequency_penalty,
+                             params.logit_bias, gen.cfg.vocab_size)
+        elif not _neutral_penalties(params):
+            raise ValueError("SamplingParams with logit penalties (repetition_penalty, presence_penalty, "
+                             "frequency_penalty, logit_bias) need ContinuousBatcher(per_request=True, penalties=True)")
         if params.lookup_tokens > 0:
             raise NotImplementedError("prompt-lookup decoding in the continuous batch is selected by the batcher's own "
                                       "keyword, ContinuousBatcher(..., lookup_tokens=K, lookup_ngram=n), not by "
@@ -929,6 +1105,10 @@ class ContinuousBatcher:
         if self.per_request:
             # every row starts at the batcher's defaults (the capture below runs the step on them)
             g._row_buffers().write(0, [RequestSampling().resolve(params, T, 0)] * MB)
+        g._pen_on = self.penalties
+        if self.penalties:
+            # neutral everywhere until an admission writes a row's own (the capture below runs on them)
+            g._penalty_buffers().reset()
         self.lookup_totals = None  # (row-steps, drafted, accepted) of the device counters, read in collect()
         if K > 0:
             # history and the verify step's buffers exist before the capture; no row is active, so the
@@ -963,6 +1143,7 @@ class ContinuousBatcher:
 
     def close(self):
         self.gen._rows_on = False
+        self.gen._pen_on = False
         self.gen.adapters = None
         if self.K > 0:
             self.gen._lk = None
@@ -1004,12 +1185,16 @@ class ContinuousBatcher:
             raise ValueError("per-request sampling settings need ContinuousBatcher(per_request=True)")
         if len(prompts) > len(self.free):
             raise ValueError(f"{len(prompts)} requests for {len(self.free)} free rows")
-        resolved = drafts = None
+        if not self.penalties and any(s is not None and s.has_penalties for s in sampling):
+            raise ValueError("logit penalty settings need ContinuousBatcher(per_request=True, penalties=True)")
+        resolved = drafts = pens = None
         if self.per_request:
             # validated before any row is taken; unseeded requests are numbered by admission
             for s in sampling:
                 if s is not None:
-                    s.validate(self.T, self.K)
+                    s.validate(self.T, self.K, g.cfg.vocab_size)
+            if self.penalties:
+                pens = [(s or RequestSampling()).resolve_penalties(self.params, g.cfg.vocab_size) for s in sampling]
             resolved = [(s or RequestSampling()).resolve(self.params, self.T, derive_seed(self.params.seed,
                                                                                          self.admitted + i))
                         for i, s in enumerate(sampling)]
@@ -1024,9 +1209,9 @@ class ContinuousBatcher:
         rows, self.free = self.free[:len(prompts)], self.free[len(prompts):]
         try:
             if slots is None:
-                self._admit_runs(rows, prompts, tags, resolved, drafts)
+                self._admit_runs(rows, prompts, tags, resolved, drafts, pens)
             else:
-                self._admit_adapter_runs(rows, prompts, tags, resolved, adapters, slots)
+                self._admit_adapter_runs(rows, prompts, tags, resolved, adapters, slots, pens)
         except BaseException:
             # all-or-nothing: rows of this call that were already prefilled leave the batch again
             # (inactive, back on the free list), so the caller can fail every request it passed
@@ -1040,7 +1225,7 @@ class ContinuousBatcher:
         self.admitted += len(prompts)
         return rows
 
-    def _admit_adapter_runs(self, rows, prompts, tags, resolved, names, slots):
+    def _admit_adapter_runs(self, rows, prompts, tags, resolved, names, slots, pens=None):
         """``_admit_runs`` per piece of consecutive rows with one adapter: each piece is prefilled with
         its slot active, unmerged (``AdapterBank.active``), under ``ops.batch_invariant`` — the
         K-extension GEMMs whatever the piece's token count, i.e. the scoring forward's numerics."""
@@ -1052,12 +1237,13 @@ class ContinuousBatcher:
                 j += 1
             g.adapter_ids[rows[i]:rows[i] + (j - i)].fill_(slots[i])
             with self.adapters.active(names[i]), ops.batch_invariant():
-                self._admit_runs(rows[i:j], prompts[i:j], tags[i:j], None if resolved is None else resolved[i:j])
+                self._admit_runs(rows[i:j], prompts[i:j], tags[i:j], None if resolved is None else resolved[i:j],
+                                 None, None if pens is None else pens[i:j])
             for r in range(i, j):
                 self.row_adapter[rows[r]] = names[r]
             i = j
 
-    def _admit_runs(self, rows, prompts, tags, resolved=None, drafts=None):
+    def _admit_runs(self, rows, prompts, tags, resolved=None, drafts=None, pens=None):
         g = self.gen
         i = 0
         while i < len(rows):
@@ -1080,7 +1266,15 @@ class ContinuousBatcher:
             g.active[b0:b0 + n].fill_(1)
             if resolved is not None:
                 g.rowp.write(b0, resolved[i:j])
-            g._emit(h_last, self.params, self.eos, self.pad_id, r0=b0)
+            if pens is not None:
+                # the prefill logits are penalised over the prompt alone (no generated token yet); the
+                # first sampled token then sits at slot S, where the first decode step appends it again
+                g.penp.write(b0, pens[i:j])
+                g.hist[b0:b0 + n, :S] = ids
+                g._emit(h_last, self.params, self.eos, self.pad_id, r0=b0, append=False)
+                g.hist[b0:b0 + n, S] = g.tok_in[b0:b0 + n]
+            else:
+                g._emit(h_last, self.params, self.eos, self.pad_id, r0=b0)
             if self.K > 0:
                 # what _enqueue does for a static batch, for these rows alone: history = the left-padded
                 # prompt, then the first sampled token at slot S (= kv_len, where the first verify step

@@ -182,6 +182,24 @@ def sample_rows(logits, inv_temp, top_k, top_p, greedy, seed, counter, active=No
     return out_tok, out_logp
 
 
+def logit_rows_penalty(logits, hist, tok_in, kv_len, kv_start, gen_len, active, rho, inv_rho, pi, phi, nbias,
+                       bias_tok, bias_val):
+    """Per-request logit penalties, in place on ``logits`` [B, V] (bf16 or fp32) before the sampler
+    reads them (``logit_rows_penalty_kernel``, one workgroup per row; its twin:
+    ``ops.reference.logit_rows_penalty``). Every parameter is a per-row tensor on the logits' device,
+    so a captured graph sees new values on replay: ``rho`` / ``inv_rho`` f32 [B] (repetition penalty
+    and its reciprocal), ``pi`` / ``phi`` f32 [B] (presence / frequency), ``nbias`` i32 [B],
+    ``bias_tok`` i32 [B, 16], ``bias_val`` f32 [B, 16]. The row's history is ``hist[b, kv_start[b] ..
+    kv_len[b]]`` (int64 [B, S], S <= ``LOGIT_ROWS_MAX_SEQ``), its last ``gen_len[b]`` tokens generated;
+    ``tok_in`` (int64 [B] or None) is appended at slot ``kv_len[b]`` first. ``active`` u8 [B] or None."""
+    args = (logits, hist, tok_in, kv_len, kv_start, gen_len, active, rho, inv_rho, pi, phi, nbias, bias_tok, bias_val)
+    if on_gpu(logits):
+        native().logit_rows_penalty(*args)
+    else:
+        ref.logit_rows_penalty(*args)
+    return logits
+
+
 # ------------------------------------------------- prompt-lookup speculative decoding bookkeeping
 def lookup_accept(sampled, logp, inp, n_draft, out_tokens, out_logp, hist, active, kv_len, pos, attn_len, kv_start,
                   gen_len, step, rng_offset, counters, eos_ids, row_max_new=None, row_stats=None):

@@ -438,3 +438,54 @@ def lookup_draft(hist, kv_len, kv_start, active, ngram, pad_id, inp, n_draft, ro
         for j in range(1, G):
             inp[b, j] = h[cont + j - 1] if j - 1 < avail else pad_id
         n_draft[b] = avail
+
+
+LOGIT_ROWS_MAX_SEQ = 4096  # history slots the logit_rows_penalty kernel stages per row
+LOGIT_ROWS_MAX_BIAS = 16
+
+
+def logit_rows_penalty(logits, hist, tok_in, kv_len, kv_start, gen_len, active, rho, inv_rho, pi, phi, nbias,
+                       bias_tok, bias_val):
+    """Twin of logit_rows_penalty_kernel (in place on ``logits`` [B, V] and, with ``tok_in``, on
+    ``hist`` [B, S]). Row b's history is ``hist[b, kv_start .. kv_len]``, its last ``gen_len`` tokens
+    generated and the ones before them the prompt; ``tok_in[b]`` is first appended at slot ``kv_len``.
+    For every distinct history token v with c occurrences among the generated tokens, in fp32 (fp64
+    for fp32 logits): ``l = l * inv_rho if l > 0 else l * rho``; ``l -= pi * [c > 0] + phi * c``;
+    then ``l += bias`` for each of the row's ``nbias`` (token, bias) pairs, in the history or not;
+    one rounding to the logits' dtype. Inactive and neutral rows are left alone."""
+    B, V = logits.shape
+    S = hist.shape[1]
+    acc = torch.float64 if logits.dtype == torch.float32 else torch.float32
+    for b in range(B):
+        if active is not None and not bool(active[b]):
+            continue
+        nb = min(max(int(nbias[b]), 0), LOGIT_ROWS_MAX_BIAS)
+        if float(rho[b]) == 1.0 and float(inv_rho[b]) == 1.0 and float(pi[b]) == 0.0 and float(phi[b]) == 0.0 \
+                and nb == 0:
+            continue
+        kl = int(kv_len[b])
+        if kl < 0 or kl >= S:
+            continue
+        if tok_in is not None:
+            hist[b, kl] = tok_in[b]
+        ks = min(max(int(kv_start[b]), 0), kl)
+        h = hist[b, ks:kl + 1]
+        n_gen = min(max(int(gen_len[b]), 0), h.numel())
+        ok = (h >= 0) & (h < V)
+        toks = torch.unique(h[ok])
+        g = h[h.numel() - n_gen:]
+        cnt = torch.bincount(g[(g >= 0) & (g < V)], minlength=V)[toks].to(acc)
+        row = logits[b]
+        l = row[toks].to(acc)
+        l = torch.where(l > 0, l * inv_rho[b].to(acc), l * rho[b].to(acc))
+        l = l - (pi[b].to(acc) * (cnt > 0).to(acc) + phi[b].to(acc) * cnt)
+        row[toks] = l.to(row.dtype)
+        for j in range(nb):
+            t = int(bias_tok[b, j])
+            if 0 <= t < V:
+                if bool((toks == t).any()):
+                    # the kernel adds the bias before its one rounding
+                    i = int(torch.nonzero(toks == t)[0])
+                    row[t] = (l[i] + bias_val[b, j].to(acc)).to(row.dtype)
+                else:
+                    row[t] = (row[t].to(acc) + bias_val[b, j].to(acc)).to(row.dtype)

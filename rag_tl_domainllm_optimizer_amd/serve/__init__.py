@@ -5,7 +5,10 @@ With ``per_request_sampling`` (config ``serve.per_request_sampling``, continuous
 body may also carry ``temperature``, ``top_k_tokens``, ``top_p``, ``do_sample``, ``seed`` and
 ``max_new_tokens``; ``timings["seed"]`` returns the seed the answer was drawn with. On a server
 with prompt-lookup decoding (``serve --eval.lookup_tokens=3``; GET /health reports ``lookup_tokens``)
-the body may also carry ``lookup_tokens`` in 0..K, the request's own draft length.
+the body may also carry ``lookup_tokens`` in 0..K, the request's own draft length. With
+``logit_penalties`` (config ``serve.logit_penalties``, needs ``per_request_sampling``) the body may
+also carry ``repetition_penalty``, ``presence_penalty``, ``frequency_penalty`` and ``logit_bias``, a
+JSON object of token id (as a string) -> bias, as in the OpenAI API.
 
 Concurrent requests are batched: the async handler awaits a future while one worker thread owns the
 GPU — by default ``serve.continuous.ContinuousEngine`` (requests join the running decode batch
@@ -19,28 +22,32 @@ from .continuous import ContinuousEngine  # noqa: F401
 
 
 SAMPLING_FIELDS = ("temperature", "top_k_tokens", "top_p", "do_sample", "seed", "max_new_tokens", "lookup_tokens")
+PENALTY_FIELDS = ("repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias")
 
 
-def request_sampling(q, max_new_tokens: Optional[int] = None, lookup_tokens: Optional[int] = None):
+def request_sampling(q, max_new_tokens: Optional[int] = None, lookup_tokens: Optional[int] = None,
+                     vocab: Optional[int] = None):
     """The ``RequestSampling`` of an /answer body (None when it sets no sampling field); ValueError
     for a value outside its range. ``top_k`` stays the document count: the token top-k is
     ``top_k_tokens``. ``lookup_tokens``: the engine's draft length K (0: lookup off; None: the
-    body's value is only checked against 0..7)."""
+    body's value is only checked against 0..7). ``vocab``: the vocabulary ``logit_bias`` tokens must
+    lie in (None: not checked here)."""
     from ..generation import RequestSampling
 
-    vals = {f: getattr(q, f, None) for f in SAMPLING_FIELDS}
+    vals = {f: getattr(q, f, None) for f in SAMPLING_FIELDS + PENALTY_FIELDS}
     if all(v is None for v in vals.values()):
         return None
     rs = RequestSampling(temperature=vals["temperature"], top_k=vals["top_k_tokens"], top_p=vals["top_p"],
                          do_sample=vals["do_sample"], seed=vals["seed"], max_new_tokens=vals["max_new_tokens"],
-                         lookup_tokens=vals["lookup_tokens"])
-    rs.validate(max_new_tokens, lookup_tokens)
+                         lookup_tokens=vals["lookup_tokens"], **{f: vals[f] for f in PENALTY_FIELDS})
+    rs.validate(max_new_tokens, lookup_tokens, vocab)
     return rs
 
 
 def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, per_request_sampling: bool = False,
-               adapters=None):
+               adapters=None, logit_penalties: bool = False):
     import asyncio
+    from typing import Dict
 
     from fastapi import FastAPI, HTTPException
     from pydantic import BaseModel
@@ -49,8 +56,14 @@ def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, pe
         raise ValueError("per_request_sampling needs continuous batching (continuous=True)")
     if adapters is not None and not continuous:
         raise ValueError("per-request adapters need continuous batching (continuous=True)")
-    engine = ContinuousEngine(pipeline, per_request_sampling=per_request_sampling, adapters=adapters) if continuous else \
-        BatchingEngine(pipeline, max_wait_s=max_wait_s)
+    if logit_penalties and not per_request_sampling:
+        raise ValueError("logit_penalties needs per_request_sampling (penalties are per-request settings)")
+    if logit_penalties:
+        engine = ContinuousEngine(pipeline, per_request_sampling=True, adapters=adapters, logit_penalties=True)
+    else:
+        engine = ContinuousEngine(pipeline, per_request_sampling=per_request_sampling, adapters=adapters) \
+            if continuous else BatchingEngine(pipeline, max_wait_s=max_wait_s)
+    vocab = getattr(getattr(getattr(pipeline, "gen", None), "cfg", None), "vocab_size", None)
     app = FastAPI(title="rag-tl-domainllm-optimizer-amd")
     app.state.engine = engine
     engine_k = getattr(engine, "lookup_tokens", 0) if continuous else 0  # the verify steps' draft length
@@ -66,12 +79,18 @@ def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, pe
         max_new_tokens: Optional[int] = None
         lookup_tokens: Optional[int] = None  # draft tokens per step, 0 .. the server's eval.lookup_tokens
         adapter: Optional[str] = None  # a loaded LoRA adapter (servers with serve.adapters); None: the base model
+        # servers with serve.logit_penalties
+        repetition_penalty: Optional[float] = None
+        presence_penalty: Optional[float] = None
+        frequency_penalty: Optional[float] = None
+        logit_bias: Optional[Dict[str, float]] = None  # token id (as a string) -> bias in [-100, 100]
 
     @app.get("/health")
     def health():
         return {"status": "ok", "docs": len(pipeline.docs), "max_batch": pipeline.max_batch,
                 "batching": "continuous" if continuous else "dynamic", "per_request_sampling": per_request_sampling,
-                "adapters": adapters.loaded() if adapters is not None else [], "lookup_tokens": engine_k}
+                "adapters": adapters.loaded() if adapters is not None else [], "lookup_tokens": engine_k,
+                "logit_penalties": bool(logit_penalties)}
 
     @app.get("/stats")
     def stats():
@@ -81,9 +100,12 @@ def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, pe
     async def answer(q: Query):
         try:
             rs = request_sampling(q, getattr(getattr(pipeline, "sampling", None), "max_new_tokens", None),
-                                  engine_k if per_request_sampling else None)
+                                  engine_k if per_request_sampling else None, vocab)
         except ValueError as e:
             raise HTTPException(status_code=422, detail=str(e))
+        if rs is not None and rs.has_penalties and per_request_sampling and not logit_penalties:
+            raise HTTPException(status_code=400, detail="logit penalties in the request need the server flag "
+                                                        "serve.logit_penalties (off on this server)")
         if rs is not None and not per_request_sampling:
             raise HTTPException(status_code=400, detail="sampling settings in the request need the server flag "
                                                         "serve.per_request_sampling (off on this server)")
@@ -107,7 +129,8 @@ def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, pe
 
 
 def serve(cfg, host: str = "127.0.0.1", port: int = 8000, max_batch: int = 16, max_wait_s: float = 0.004,
-          continuous: bool = True, per_request_sampling: Optional[bool] = None, adapters=None):
+          continuous: bool = True, per_request_sampling: Optional[bool] = None, adapters=None,
+          logit_penalties: Optional[bool] = None):
     import uvicorn
 
     from ..cli import apply_fp4, build_stack
@@ -125,6 +148,8 @@ def serve(cfg, host: str = "127.0.0.1", port: int = 8000, max_batch: int = 16, m
                       cfg.ppo.max_prompt_tokens, max_batch=max_batch)
     if per_request_sampling is None:
         per_request_sampling = cfg.serve.per_request_sampling
+    if logit_penalties is None:
+        logit_penalties = cfg.serve.logit_penalties
     # per-request adapters: serve.adapters {name: PEFT directory}, plus / overridden by ``adapters``
     named = dict(getattr(cfg.serve, "adapters", None) or {})
     named.update(adapters or {})
@@ -142,4 +167,5 @@ def serve(cfg, host: str = "127.0.0.1", port: int = 8000, max_batch: int = 16, m
         bank = AdapterBank(st["policy"], slots=max(8, len(named)), r_max=next(r for r in (8, 16, 32, 64) if r >= max(ranks)))
         for name, path in named.items():
             bank.load(name, path)
-    uvicorn.run(create_app(rag, max_wait_s, continuous, per_request_sampling, bank), host=host, port=port)
+    uvicorn.run(create_app(rag, max_wait_s, continuous, per_request_sampling, bank, logit_penalties), host=host,
+                port=port)

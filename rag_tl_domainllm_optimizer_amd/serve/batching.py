@@ -35,7 +35,8 @@ class BatchingEngine:
         if sampling is not None:
             # a request group runs to completion under the pipeline's one SamplingParams
             raise ValueError("BatchingEngine does not support per-request sampling settings; use "
-                             "ContinuousEngine(per_request_sampling=True)")
+                             "ContinuousEngine(per_request_sampling=True) (and logit_penalties=True for "
+                             "repetition_penalty, presence_penalty, frequency_penalty and logit_bias)")
         if self._closed:
             raise RuntimeError("BatchingEngine is closed")
         fut: cf.Future = cf.Future()

@@ -27,6 +27,10 @@ lookup_ngram=n)``; the batcher's ``SamplingParams`` carry ``lookup_tokens=0``). 
 accepted draft tokens); ``stats`` keeps the running totals ``lookup_steps`` / ``lookup_drafted`` /
 ``lookup_accepted`` over all rows. With ``per_request_sampling`` a request may bring its own
 ``RequestSampling.lookup_tokens`` in 0..K. Not together with adapters.
+
+``logit_penalties=True`` (needs ``per_request_sampling``; not with prompt-lookup decoding): a request's
+``RequestSampling`` may also carry ``repetition_penalty``, ``presence_penalty``, ``frequency_penalty``
+and ``logit_bias`` (``ContinuousBatcher(penalties=True)``).
 """
 from __future__ import annotations
 
@@ -46,7 +50,11 @@ from ..rag.prompt import extract_answer
 
 
 class ContinuousEngine:
-    def __init__(self, pipeline, chunk: int = 4, per_request_sampling: bool = False, adapters=None):
+    def __init__(self, pipeline, chunk: int = 4, per_request_sampling: bool = False, adapters=None,
+                 logit_penalties: bool = False):
+        if logit_penalties and not per_request_sampling:
+            raise ValueError("logit_penalties needs per_request_sampling=True (penalties are per-request settings)")
+        self.logit_penalties = bool(logit_penalties)
         self.lookup_tokens = int(pipeline.sampling.lookup_tokens)
         self.lookup_ngram = int(getattr(pipeline.sampling, "lookup_ngram", 2))
         layers = getattr(pipeline.gen.model, "layers", None)
@@ -83,7 +91,10 @@ class ContinuousEngine:
         if sampling is not None:
             if not self.per_request_sampling:
                 raise ValueError("per-request sampling settings need ContinuousEngine(per_request_sampling=True)")
-            sampling.validate(self.pipeline.sampling.max_new_tokens, self.lookup_tokens)
+            if sampling.has_penalties and not self.logit_penalties:
+                raise ValueError("logit penalty settings in the request need ContinuousEngine(logit_penalties=True)")
+            sampling.validate(self.pipeline.sampling.max_new_tokens, self.lookup_tokens,
+                              self.pipeline.gen.cfg.vocab_size)
         with self._lock:
             if self._closed:
                 if self._dead is not None:
@@ -191,7 +202,11 @@ class ContinuousEngine:
                 cb = ContinuousBatcher(p.gen, dataclasses.replace(p.sampling, lookup_tokens=0),
                                        pad_id=p.tok.pad_token_id, eos_ids=[p.tok.eos_token_id],
                                        per_request=self.per_request_sampling, adapters=self.adapters,
-                                       lookup_tokens=self.lookup_tokens, lookup_ngram=self.lookup_ngram)
+                                       lookup_tokens=self.lookup_tokens, lookup_ngram=self.lookup_ngram,
+                                       penalties=self.logit_penalties)
+            elif self.logit_penalties:
+                cb = ContinuousBatcher(p.gen, p.sampling, pad_id=p.tok.pad_token_id, eos_ids=[p.tok.eos_token_id],
+                                       per_request=True, adapters=self.adapters, penalties=True)
             else:
                 cb = ContinuousBatcher(p.gen, p.sampling, pad_id=p.tok.pad_token_id, eos_ids=[p.tok.eos_token_id],
                                        per_request=self.per_request_sampling, adapters=self.adapters)
