@@ -115,6 +115,8 @@ int rt_logit_rows_max_seq();
 int rt_logit_rows_penalty(void*, int, long, long, int, long*, int, const long*, const int*, const int*, const int*,
                           const uint8_t*, const float*, const float*, const float*, const float*, const int*, const int*,
                           const float*, hipStream_t);
+int rt_stop_rows(const long*, long, int, int*, uint8_t*, const int*, const uint8_t*, int, int, int, const int*, const int*,
+                 const uint8_t*, const int*, const int*, int*, int*, int*, int*, long, hipStream_t);
 }
 
 namespace {
@@ -1733,6 +1735,38 @@ void logit_rows_penalty(Tensor logits, Tensor hist, const optional<Tensor>& tok_
            "logit_rows_penalty");
 }
 
+// Per-request stop strings and stop token ids: one wave per row scans the row's new tokens through the
+// vocabulary byte table (stop_rows.hip). Every state buffer is a per-row device buffer.
+void stop_rows(const Tensor& out_tokens, Tensor gen_len, Tensor active, const Tensor& offsets, const Tensor& blob,
+               bool strip_first_space, const Tensor& n_stop, const Tensor& stop_len, const Tensor& stop_bytes,
+               const Tensor& n_stop_tok, const Tensor& stop_tok, Tensor seen, Tensor nbytes, Tensor stop_hit,
+               Tensor stop_at) {
+  CHECK_CUDA(out_tokens); CHECK_I64(out_tokens); CHECK_ROWS(out_tokens);
+  const int64_t B = out_tokens.size(0), T = out_tokens.size(1);
+  CHECK_I32(gen_len); CHECK_I32(offsets); CHECK_I32(n_stop); CHECK_I32(stop_len); CHECK_I32(n_stop_tok);
+  CHECK_I32(stop_tok); CHECK_I32(seen); CHECK_I32(nbytes); CHECK_I32(stop_hit); CHECK_I32(stop_at);
+  TORCH_CHECK(active.scalar_type() == at::kByte || active.scalar_type() == at::kBool, "active must be uint8 or bool");
+  TORCH_CHECK(blob.scalar_type() == at::kByte && stop_bytes.scalar_type() == at::kByte,
+              "stop_rows: blob and stop_bytes must be uint8");
+  auto vec = [&](const Tensor& t, const char* name, int64_t n) {
+    TORCH_CHECK(t.is_cuda() && t.get_device() == out_tokens.get_device(), "stop_rows: ", name,
+                " must be on the tokens' device");
+    TORCH_CHECK(t.is_contiguous() && t.numel() == n, "stop_rows: ", name, " must be contiguous with ", n, " elements");
+  };
+  TORCH_CHECK(offsets.numel() >= 2, "stop_rows: offsets must hold V + 1 entries");
+  vec(gen_len, "gen_len", B); vec(active, "active", B); vec(offsets, "offsets", offsets.numel());
+  vec(blob, "blob", blob.numel()); vec(n_stop, "n_stop", B); vec(stop_len, "stop_len", B * 4);
+  vec(stop_bytes, "stop_bytes", B * 4 * 32); vec(n_stop_tok, "n_stop_tok", B); vec(stop_tok, "stop_tok", B * 8);
+  vec(seen, "seen", B); vec(nbytes, "nbytes", B); vec(stop_hit, "stop_hit", B); vec(stop_at, "stop_at", B);
+  check_rc(rt_stop_rows((const long*)out_tokens.data_ptr(), out_tokens.stride(0), (int)T, gen_len.data_ptr<int>(),
+                        (uint8_t*)active.data_ptr(), offsets.data_ptr<int>(), (const uint8_t*)blob.data_ptr(),
+                        (int)offsets.numel() - 1, (int)blob.numel(), strip_first_space ? 1 : 0, n_stop.data_ptr<int>(),
+                        stop_len.data_ptr<int>(), (const uint8_t*)stop_bytes.data_ptr(), n_stop_tok.data_ptr<int>(),
+                        stop_tok.data_ptr<int>(), seen.data_ptr<int>(), nbytes.data_ptr<int>(),
+                        stop_hit.data_ptr<int>(), stop_at.data_ptr<int>(), B, cur_stream()),
+           "stop_rows");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1853,6 +1887,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("active"), py::arg("rho"), py::arg("inv_rho"), py::arg("pi"), py::arg("phi"), py::arg("nbias"),
         py::arg("bias_tok"), py::arg("bias_val"));
   m.def("logit_rows_max_seq", []() { return rt_logit_rows_max_seq(); }, "history slots logit_rows_penalty supports");
+  m.def("stop_rows", &stop_rows, "per-request stop strings / stop token ids over the rows' new tokens",
+        py::arg("out_tokens"), py::arg("gen_len"), py::arg("active"), py::arg("offsets"), py::arg("blob"),
+        py::arg("strip_first_space"), py::arg("n_stop"), py::arg("stop_len"), py::arg("stop_bytes"),
+        py::arg("n_stop_tok"), py::arg("stop_tok"), py::arg("seen"), py::arg("nbytes"), py::arg("stop_hit"),
+        py::arg("stop_at"));
   ragtl::bind_tokenizer(m);
   ragtl::bind_ivf_host(m);
 }

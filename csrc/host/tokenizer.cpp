@@ -177,6 +177,49 @@ class Tokenizer {
     return o;
   }
 
+  // What token `id` adds to the decoded text when it is not the first token (decode() with
+  // skip_special): concatenating these over an id list, and dropping one leading space when
+  // strip_first_space() is set and the concatenation starts with one, gives decode(ids, true).
+  std::string token_bytes(int64_t id) const {
+    std::string o;
+    if (id < 0 || id >= (int64_t)inv_.size()) return o;
+    const std::string& tok = inv_[id];
+    if (specials_.count(tok)) return o;
+    if (kind_ == "bpe") {
+      for (auto& ch : utf8_chars(tok)) {
+        auto it = bytemap().dec.find(ch);
+        if (it != bytemap().dec.end()) o.push_back((char)it->second);
+        else o += ch;
+      }
+    } else if (kind_ == "sp_bpe") {
+      if (byte_fallback_ && tok.size() == 6 && tok[0] == '<' && tok[1] == '0' && tok[2] == 'x' && tok[5] == '>') {
+        o.push_back((char)std::stoi(tok.substr(3, 2), nullptr, 16));
+        return o;
+      }
+      for (auto& ch : utf8_chars(tok)) o += (ch == "\xE2\x96\x81") ? std::string(" ") : ch;
+    } else if (kind_ == "wordpiece" && !cont_.empty() && tok.compare(0, cont_.size(), cont_) == 0) {
+      o = tok.substr(cont_.size());
+    } else {
+      o = " " + tok;
+    }
+    return o;
+  }
+  // the start rule of decode(): word kinds put no space before the first word, sp_bpe with a prefix
+  // space drops one leading space
+  bool strip_first_space() const {
+    return kind_ == "wordlevel" || kind_ == "wordpiece" || (kind_ == "sp_bpe" && prefix_space_);
+  }
+  // the whole table: offsets [V + 1] into one blob
+  std::pair<std::vector<int32_t>, py::bytes> token_bytes_table() const {
+    std::vector<int32_t> offs(inv_.size() + 1, 0);
+    std::string blob;
+    for (size_t i = 0; i < inv_.size(); ++i) {
+      blob += token_bytes((int64_t)i);
+      offs[i + 1] = (int32_t)blob.size();
+    }
+    return {offs, py::bytes(blob)};
+  }
+
   int64_t token_to_id(const std::string& t) const {
     auto it = vocab_.find(t);
     return it == vocab_.end() ? -1 : it->second;
@@ -347,6 +390,9 @@ void bind_tokenizer(py::module& m) {
       .def("encode", &Tokenizer::encode)
       .def("encode_batch", &Tokenizer::encode_batch, py::arg("texts"), py::arg("nthreads") = 8)
       .def("decode", &Tokenizer::decode, py::arg("ids"), py::arg("skip_special") = true)
+      .def("token_bytes", [](const Tokenizer& t, int64_t id) { return py::bytes(t.token_bytes(id)); })
+      .def("token_bytes_table", &Tokenizer::token_bytes_table)
+      .def("strip_first_space", &Tokenizer::strip_first_space)
       .def("token_to_id", &Tokenizer::token_to_id)
       .def("id_to_token", &Tokenizer::id_to_token)
       .def("vocab_size", &Tokenizer::vocab_size);

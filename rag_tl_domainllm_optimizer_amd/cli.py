@@ -416,6 +416,10 @@ def cmd_serve(cfg, args):
         cfg.serve.logit_penalties = args.logit_penalties
     if cfg.serve.logit_penalties and not cfg.serve.per_request_sampling:
         raise SystemExit("serve: --logit-penalties (serve.logit_penalties) needs --per-request-sampling")
+    if args.stop_sequences is not None:
+        cfg.serve.stop_sequences = args.stop_sequences
+    if cfg.serve.stop_sequences and not cfg.serve.per_request_sampling:
+        raise SystemExit("serve: --stop-sequences (serve.stop_sequences) needs --per-request-sampling")
     adapters = {}
     for item in args.adapter or []:
         name, sep, path = item.partition("=")
@@ -423,7 +427,7 @@ def cmd_serve(cfg, args):
             raise SystemExit(f"serve: --adapter takes name=path, got {item!r}")
         adapters[name] = path
     serve(cfg, host=args.host, port=args.port, per_request_sampling=cfg.serve.per_request_sampling, adapters=adapters,
-          logit_penalties=cfg.serve.logit_penalties)
+          logit_penalties=cfg.serve.logit_penalties, stop_sequences=cfg.serve.stop_sequences)
 
 
 def cmd_bench(cfg, args, rest):
@@ -461,6 +465,9 @@ def main(argv: Optional[List[str]] = None):
     ap.add_argument("--logit-penalties", dest="logit_penalties", action=argparse.BooleanOptionalAction, default=None,
                     help="serve: accept per-request repetition / presence / frequency penalties and logit_bias "
                          "(serve.logit_penalties; needs --per-request-sampling)")
+    ap.add_argument("--stop-sequences", dest="stop_sequences", action=argparse.BooleanOptionalAction, default=None,
+                    help="serve: accept per-request stop strings and stop token ids (serve.stop_sequences; needs "
+                         "--per-request-sampling)")
     ap.add_argument("--adapter", action="append", default=[],
                     help="serve: name=path of a PEFT LoRA adapter a request may pick (repeatable; serve.adapters)")
     ap.add_argument("--env", action="append", default=[], help="launch: KEY=VALUE set for every rank (repeatable)")

@@ -72,6 +72,10 @@ class ServeSection:
     # requests may also carry repetition_penalty / presence_penalty / frequency_penalty / logit_bias
     # (needs per_request_sampling; one more small launch per decode step; not with eval.lookup_tokens)
     logit_penalties: bool = False
+    # requests may also carry stop (at most 4 strings of 1..32 bytes) / stop_token_ids (at most 8):
+    # the answer ends where the first of them begins (needs per_request_sampling; one more small
+    # launch per decode step)
+    stop_sequences: bool = False
     # LoRA adapters resident over the served base model, name -> PEFT directory: a request picks one
     # with its "adapter" field (continuous batching, at most 16 rows); empty: one model, as before
     adapters: Dict[str, str] = field(default_factory=dict)

@@ -29,6 +29,9 @@ class SamplingParams:
     top_p: float = 1.0
     do_sample: bool = True              # reference rl.py:42
     max_length: Optional[int] = None    # reference semantics: prompt + new tokens (rl.py:40)
+    # stop strings / stop token ids: the defaults of a ``ContinuousBatcher(stops=True)``; empty = off.
+    # stop: one string or at most 4 strings of 1..32 UTF-8 bytes; stop_token_ids: at most 8 ids
+    stop: Optional[object] = None
     stop_token_ids: Sequence[int] = ()
     seed: int = 0
     # prompt-lookup speculative decoding (batch-1..8 RAG answers): K draft tokens per step, proposed
@@ -99,6 +102,45 @@ def _check_penalties(rho, pi, phi, logit_bias, vocab=None):
     return pairs
 
 
+def _check_stops(stop, stop_token_ids, vocab=None):
+    """``stop`` (None, a string or a sequence of strings) and ``stop_token_ids`` (None or a sequence
+    of ids) as (tuple of UTF-8 byte strings, tuple of ids); ValueError for more than 4 strings, a
+    string that is empty or longer than 32 bytes, a duplicate string, more than 8 ids, or an id that is
+    no integer in [0, vocab)."""
+    strings = () if stop is None else (stop,) if isinstance(stop, (str, bytes)) else tuple(stop)
+    if len(strings) > ops.STOP_MAX_STR:
+        raise ValueError(f"stop: {len(strings)} strings, at most {ops.STOP_MAX_STR} per request")
+    out = []
+    for st in strings:
+        if not isinstance(st, (str, bytes)):
+            raise ValueError(f"stop: entries are strings, got {st!r}")
+        raw = st.encode("utf-8") if isinstance(st, str) else bytes(st)
+        if not 1 <= len(raw) <= ops.STOP_MAX_LEN:
+            raise ValueError(f"stop: {st!r} is {len(raw)} bytes of UTF-8, must be 1..{ops.STOP_MAX_LEN}")
+        if raw in out:
+            raise ValueError(f"stop: {st!r} given twice")
+        out.append(raw)
+    ids = () if stop_token_ids is None else tuple(stop_token_ids)
+    if len(ids) > ops.STOP_MAX_TOK:
+        raise ValueError(f"stop_token_ids: {len(ids)} ids, at most {ops.STOP_MAX_TOK} per request")
+    uniq = []
+    for t in ids:
+        if isinstance(t, bool) or not isinstance(t, int) or t < 0 or (vocab is not None and t >= vocab):
+            raise ValueError(f"stop_token_ids: {t!r} must be an integer in [0, "
+                             f"{vocab if vocab is not None else 'the vocabulary size'})")
+        if t not in uniq:
+            uniq.append(t)
+    return tuple(out), tuple(uniq)
+
+
+def _neutral_stops(params) -> bool:
+    return not params.stop and not tuple(params.stop_token_ids or ())
+
+
+_STOPS_NEED = ("stop strings and stop token ids (stop, stop_token_ids) are served by ContinuousBatcher(per_request=True, "
+               "stops=True, token_bytes=...) only")
+
+
 _MIX = 0x9E3779B97F4A7C15  # 2**64 / golden ratio: spreads consecutive integers over 64 bits
 
 
@@ -131,6 +173,16 @@ class RequestSampling:
     presence_penalty: Optional[float] = None
     frequency_penalty: Optional[float] = None
     logit_bias: Optional[object] = None
+    # where the answer ends, only for batchers built with ``stops=True`` (None: the batcher's
+    # ``SamplingParams`` value): one string or at most 4 strings of 1..32 UTF-8 bytes, searched in the
+    # text of the generated tokens, and at most 8 token ids; the matched text is not part of the answer
+    stop: Optional[object] = None
+    stop_token_ids: Optional[Sequence[int]] = None
+
+    @property
+    def has_stops(self) -> bool:
+        """True when the request sets a stop field (empty values included)"""
+        return self.stop is not None or self.stop_token_ids is not None
 
     @property
     def has_penalties(self) -> bool:
@@ -143,6 +195,7 @@ class RequestSampling:
         ``lookup``: the batcher's draft length K, 0 = lookup off, None = not checked here; ``vocab``:
         the vocabulary size bias tokens must lie in, None = not checked here)."""
         _check_penalties(self.repetition_penalty, self.presence_penalty, self.frequency_penalty, self.logit_bias, vocab)
+        _check_stops(self.stop, self.stop_token_ids, vocab)
         if self.lookup_tokens is not None:
             if not (isinstance(self.lookup_tokens, int) and 0 <= self.lookup_tokens <= 7):
                 raise ValueError(f"lookup_tokens = {self.lookup_tokens}: must be an integer in [0, 7]")
@@ -183,6 +236,11 @@ class RequestSampling:
         phi = float(pick(self.frequency_penalty, params.frequency_penalty))
         pairs = _check_penalties(rho, pi, phi, pick(self.logit_bias, params.logit_bias), vocab)
         return rho, pi, phi, pairs
+
+    def resolve_stops(self, params: SamplingParams, vocab: Optional[int] = None):
+        """((stop string bytes, ...), (stop token id, ...)) with the batcher's defaults filled in"""
+        return _check_stops(params.stop if self.stop is None else self.stop,
+                            params.stop_token_ids if self.stop_token_ids is None else self.stop_token_ids, vocab)
 
 
 class _RowParams:
@@ -250,6 +308,53 @@ class _RowPenalties:
                 torch.tensor([len(r[3]) for r in rows], dtype=torch.int32), tok, val)
         for t, col in zip(self.tensors(), cols):
             t[b0:b0 + n].copy_(col)
+
+
+class _RowStops:
+    """Static per-row stop strings / stop token ids and the scan state of ``ops.stop_rows`` (device
+    memory the captured decode step reads and writes); every row starts without stops."""
+
+    def __init__(self, B: int, device):
+        i32 = dict(dtype=torch.int32, device=device)
+        self.n_stop = torch.zeros(B, **i32)
+        self.stop_len = torch.zeros(B, ops.STOP_MAX_STR, **i32)
+        self.stop_bytes = torch.zeros(B, ops.STOP_MAX_STR, ops.STOP_MAX_LEN, dtype=torch.uint8, device=device)
+        self.n_stop_tok = torch.zeros(B, **i32)
+        self.stop_tok = torch.zeros(B, ops.STOP_MAX_TOK, **i32)
+        self.seen = torch.zeros(B, **i32)      # generated tokens already scanned
+        self.nbytes = torch.zeros(B, **i32)    # table bytes already scanned (a stripped leading space included)
+        self.stop_hit = torch.full((B,), -1, **i32)  # -1 none, 0..3 the string, 4 + j stop id j
+        self.stop_at = torch.zeros(B, **i32)   # byte offset in the stream text where the answer ends
+
+    def tensors(self):
+        return [self.n_stop, self.stop_len, self.stop_bytes, self.n_stop_tok, self.stop_tok, self.seen, self.nbytes,
+                self.stop_hit, self.stop_at]
+
+    def reset(self):
+        for t in self.tensors():
+            t.fill_(-1 if t is self.stop_hit else 0)
+
+    def write(self, b0: int, rows):
+        """rows: ``RequestSampling.resolve_stops`` tuples of rows b0..; the scan state of the rows
+        starts over (host-to-device copies, outside any graph)"""
+        n = len(rows)
+        slen = torch.zeros(n, ops.STOP_MAX_STR, dtype=torch.int32)
+        sbytes = torch.zeros(n, ops.STOP_MAX_STR, ops.STOP_MAX_LEN, dtype=torch.uint8)
+        stok = torch.zeros(n, ops.STOP_MAX_TOK, dtype=torch.int32)
+        for i, (strings, ids) in enumerate(rows):
+            for j, raw in enumerate(strings):
+                slen[i, j] = len(raw)
+                sbytes[i, j, :len(raw)] = torch.tensor(list(raw), dtype=torch.uint8)
+            for j, t in enumerate(ids):
+                stok[i, j] = t
+        zero = torch.zeros(n, dtype=torch.int32)
+        cols = (torch.tensor([len(r[0]) for r in rows], dtype=torch.int32), slen, sbytes,
+                torch.tensor([len(r[1]) for r in rows], dtype=torch.int32), stok, zero, zero, zero - 1, zero)
+        for t, col in zip(self.tensors(), cols):
+            t[b0:b0 + n].copy_(col)
+
+    def rows(self, r0: int, r1: int):
+        return [t[r0:r1] for t in self.tensors()]
 
 
 def _neutral_penalties(params: SamplingParams) -> bool:
@@ -405,6 +510,12 @@ class Generator:
         # allocated on first use; _pen_on puts ops.logit_rows_penalty in front of the per-row sampler
         self.penp = None
         self._pen_on = False
+        # per-request stop strings / stop token ids (ContinuousBatcher(stops=True)): the vocabulary
+        # byte table, the per-row stop buffers (allocated on first use); _stop_on puts ops.stop_rows
+        # behind the bookkeeping kernel
+        self.stopp = None
+        self.token_bytes = None
+        self._stop_on = False
 
     # ------------------------------------------------------------------ one decode step (device only)
     def _bucket(self, B: int) -> int:
@@ -445,6 +556,16 @@ class Generator:
         if self.hist is None:
             self.hist = torch.zeros(self.max_batch, self.max_seq, dtype=torch.long, device=self.device)
         return self.penp
+
+    def _stop_buffers(self) -> _RowStops:
+        if self.stopp is None:
+            self.stopp = _RowStops(self.max_batch, self.device)
+        return self.stopp
+
+    def _stop_rows(self, r0: int, r1: int):
+        """The stop scan of rows [r0, r1) over the tokens the bookkeeping just emitted"""
+        ops.stop_rows(self.out_tokens[r0:r1], self.gen_len[r0:r1], self.active[r0:r1], self.token_bytes,
+                      *self.stopp.rows(r0, r1))
 
     def _row_buffers(self) -> _RowParams:
         if self.rowp is None:
@@ -511,6 +632,9 @@ class Generator:
                               self.out_tokens[:nb], self.out_logp[:nb], self.hist[:nb], self.active[:nb],
                               self.kv_len[:nb], self.pos[:nb], self.attn_len[:nb], self.kv_start[:nb],
                               self.gen_len[:nb], self.step, self.rng_offset, st.counters, eos_ids)
+        if self._stop_on and self._lk_rows:
+            # before the draft: a stopped row gets no further inputs
+            self._stop_rows(0, nb)
         self._draft(params, pad_id)
 
     def _draft(self, params: SamplingParams, pad_id: int, r0: int = 0, r1: Optional[int] = None):
@@ -566,6 +690,8 @@ class Generator:
                                        self.attn_len[r0:r1], self.kv_start[r0:r1])
         else:
             self._update_cpu(eos_ids, pad_id, r0, r1)
+        if rp is not None and self._stop_on:
+            self._stop_rows(r0, r1)
 
     def _update_cpu(self, eos_ids, pad_id, r0: int = 0, r1: Optional[int] = None):
         """CPU twin of decode_update_kernel over rows [r0, r1): each active row writes at its own
@@ -636,8 +762,11 @@ class Generator:
             raise ValueError("logit penalties (repetition_penalty, presence_penalty, frequency_penalty, logit_bias) "
                              "are served by ContinuousBatcher(per_request=True, penalties=True) only, not by "
                              "Generator.generate")
+        if not _neutral_stops(params):
+            raise ValueError(_STOPS_NEED + ", not by Generator.generate")
         self._rows_on = False  # a batch under one SamplingParams: the scalar sampler and its stream
         self._pen_on = False
+        self._stop_on = False
         self._lk_rows = False
         K = params.lookup_tokens
         # the last verify step may append K rows past the last emitted token
@@ -742,13 +871,20 @@ class Generator:
             key = key + ("adapters",)  # slots are read from the row buffer: one graph per bucket whatever the mix
         if self._pen_on:
             key = key + ("penalties",)  # the step carries the penalty launch; settings are read from the row buffers
+        keep = (eos,)
+        if self._stop_on:
+            # the step carries the stop scan; stops are read from the row buffers. The byte table's
+            # device memory is baked into the step: the key names it and the graph keeps it alive, so a
+            # batcher with another table captures its own step instead of replaying this one
+            key = key + ("stops", self.token_bytes.key)
+            keep = (eos, self.token_bytes.offsets, self.token_bytes.blob)
         if self._lk is not None:
             # a verify step is its own graph per (K, n-gram length); plain keys are unchanged
             key = key + ("lookup", params.lookup_tokens, params.lookup_ngram)
             step = self._step_verify
         if self.use_graph and self.runner.needs(key):
             # the EOS tensor is created per call: the runner keeps the captured one alive
-            self.runner.capture(lambda: step(params, eos, pad_id), key, keep=(eos,), restore=self._state())
+            self.runner.capture(lambda: step(params, eos, pad_id), key, keep=keep, restore=self._state())
 
     def _replay(self, params, eos, pad_id):
         if self.use_graph:
@@ -768,6 +904,8 @@ class Generator:
             st += self.rowp.tensors()
         if self._pen_on:
             st += [self.hist] + self.penp.tensors()
+        if self._stop_on:
+            st += self.stopp.tensors()
         return st
 
 
@@ -991,6 +1129,13 @@ class FinishedRow:
     # draft tokens among its output (len(tokens) == 1 + lookup_steps + lookup_accepted)
     lookup_steps: Optional[int] = None
     lookup_accepted: Optional[int] = None
+    # why the row left the batch: "stop" (a stop string or stop token id, batchers with stops=True),
+    # "eos" or "length"
+    finish_reason: Optional[str] = None
+    # finish_reason == "stop": the matched stop string or stop token id, and the length in bytes of
+    # the stream text to keep (the UTF-8 bytes of decode(tokens) up to where the match begins)
+    stop: Optional[object] = None
+    text_bytes: Optional[int] = None
 
 
 class ContinuousBatcher:
@@ -1035,14 +1180,45 @@ class ContinuousBatcher:
     of a batcher without the flag. ``max_seq`` at most ``ops.LOGIT_ROWS_MAX_SEQ``; not together with
     ``lookup_tokens``. With the flag off no buffer, graph key or launch differs.
 
+    ``stops=True, token_bytes=ops.TokenBytes`` (needs ``per_request``): a ``RequestSampling`` may also
+    bring ``stop`` (one string or at most 4 strings of 1..32 UTF-8 bytes) and ``stop_token_ids`` (at
+    most 8; defaults: the ``SamplingParams`` fields of the same names). ``ops.stop_rows`` runs behind
+    the bookkeeping kernel of the captured step (between accept and draft of a verify step) and
+    eagerly after an admission's first token: it searches the stream text of the row's generated
+    tokens (their entries in the vocabulary byte table; the prompt is never searched) and ends the row
+    at the first token that completes a stop string or is a stop id. ``FinishedRow.finish_reason`` is
+    then ``"stop"``, ``stop`` the matched string or id, and ``text_bytes`` the bytes of
+    ``decode(tokens)`` to keep; ``tokens`` run up to and including the token that completed the
+    match. One graph per bucket whatever the mix; rows without stops are bit for bit those of a
+    batcher without the flag. Works with ``penalties``, ``adapters`` and ``lookup_tokens``; with
+    lookup a stop can drop tokens a verify step had already accepted, which a row's
+    ``lookup_accepted`` still counts. With the flag off no buffer, graph key or launch differs.
+
     Usage: ``admit(prompt_ids, tag)`` while ``free_rows()``; ``step(n)``; ``collect()`` returns the
     rows that finished (a host read of the per-row flags once per call)."""
 
     def __init__(self, gen: Generator, params: SamplingParams, pad_id: int = 0, eos_ids: Sequence[int] = (),
                  per_request: bool = False, adapters=None, lookup_tokens: int = 0, lookup_ngram: int = 2,
-                 penalties: bool = False):
+                 penalties: bool = False, stops: bool = False, token_bytes=None):
         if adapters is not None:
             _check_bank(gen, params, adapters)
+        self.stops = bool(stops)
+        if self.stops:
+            if not per_request:
+                raise ValueError("stop strings are per-request settings: ContinuousBatcher(stops=True) needs "
+                                 "per_request=True")
+            if not isinstance(token_bytes, ops.TokenBytes):
+                raise ValueError("ContinuousBatcher(stops=True) needs token_bytes=ops.TokenBytes.from_tokenizer(...), "
+                                 "the vocabulary byte table stop strings are searched through")
+            if token_bytes.vocab_size != gen.cfg.vocab_size:
+                raise ValueError(f"stop strings: the byte table has {token_bytes.vocab_size} entries, the model's "
+                                 f"vocabulary {gen.cfg.vocab_size}")
+            if token_bytes.device != gen.device:
+                raise ValueError(f"stop strings: the byte table is on {token_bytes.device}, the generator on "
+                                 f"{gen.device}")
+            _check_stops(params.stop, params.stop_token_ids, gen.cfg.vocab_size)
+        elif not _neutral_stops(params):
+            raise ValueError("SamplingParams with " + _STOPS_NEED + " (the stops flag is off)")
         self.penalties = bool(penalties)
         if self.penalties:
             if not per_request:
@@ -1109,6 +1285,12 @@ class ContinuousBatcher:
         if self.penalties:
             # neutral everywhere until an admission writes a row's own (the capture below runs on them)
             g._penalty_buffers().reset()
+        g._stop_on = self.stops
+        self.row_stops = {}  # row -> (stop string bytes, stop token ids) of its request
+        if self.stops:
+            # no row has stops until an admission writes its own (the capture below runs on them)
+            g.token_bytes = token_bytes
+            g._stop_buffers().reset()
         self.lookup_totals = None  # (row-steps, drafted, accepted) of the device counters, read in collect()
         if K > 0:
             # history and the verify step's buffers exist before the capture; no row is active, so the
@@ -1144,6 +1326,7 @@ class ContinuousBatcher:
     def close(self):
         self.gen._rows_on = False
         self.gen._pen_on = False
+        self.gen._stop_on = False
         self.gen.adapters = None
         if self.K > 0:
             self.gen._lk = None
@@ -1187,7 +1370,10 @@ class ContinuousBatcher:
             raise ValueError(f"{len(prompts)} requests for {len(self.free)} free rows")
         if not self.penalties and any(s is not None and s.has_penalties for s in sampling):
             raise ValueError("logit penalty settings need ContinuousBatcher(per_request=True, penalties=True)")
-        resolved = drafts = pens = None
+        if not self.stops and any(s is not None and s.has_stops for s in sampling):
+            raise ValueError("stop / stop_token_ids in the request need ContinuousBatcher(per_request=True, stops=True, "
+                             "token_bytes=...): the stops flag is off")
+        resolved = drafts = pens = stops = None
         if self.per_request:
             # validated before any row is taken; unseeded requests are numbered by admission
             for s in sampling:
@@ -1195,6 +1381,8 @@ class ContinuousBatcher:
                     s.validate(self.T, self.K, g.cfg.vocab_size)
             if self.penalties:
                 pens = [(s or RequestSampling()).resolve_penalties(self.params, g.cfg.vocab_size) for s in sampling]
+            if self.stops:
+                stops = [(s or RequestSampling()).resolve_stops(self.params, g.cfg.vocab_size) for s in sampling]
             resolved = [(s or RequestSampling()).resolve(self.params, self.T, derive_seed(self.params.seed,
                                                                                          self.admitted + i))
                         for i, s in enumerate(sampling)]
@@ -1209,9 +1397,9 @@ class ContinuousBatcher:
         rows, self.free = self.free[:len(prompts)], self.free[len(prompts):]
         try:
             if slots is None:
-                self._admit_runs(rows, prompts, tags, resolved, drafts, pens)
+                self._admit_runs(rows, prompts, tags, resolved, drafts, pens, stops)
             else:
-                self._admit_adapter_runs(rows, prompts, tags, resolved, adapters, slots, pens)
+                self._admit_adapter_runs(rows, prompts, tags, resolved, adapters, slots, pens, stops)
         except BaseException:
             # all-or-nothing: rows of this call that were already prefilled leave the batch again
             # (inactive, back on the free list), so the caller can fail every request it passed
@@ -1219,13 +1407,14 @@ class ContinuousBatcher:
                 self.rows.pop(b, None)
                 self.row_seed.pop(b, None)
                 self.row_adapter.pop(b, None)
+                self.row_stops.pop(b, None)
             g.active[torch.tensor(rows, device=g.device)] = 0
             self.free = sorted(self.free + rows)
             raise
         self.admitted += len(prompts)
         return rows
 
-    def _admit_adapter_runs(self, rows, prompts, tags, resolved, names, slots, pens=None):
+    def _admit_adapter_runs(self, rows, prompts, tags, resolved, names, slots, pens=None, stops=None):
         """``_admit_runs`` per piece of consecutive rows with one adapter: each piece is prefilled with
         its slot active, unmerged (``AdapterBank.active``), under ``ops.batch_invariant`` — the
         K-extension GEMMs whatever the piece's token count, i.e. the scoring forward's numerics."""
@@ -1238,12 +1427,12 @@ class ContinuousBatcher:
             g.adapter_ids[rows[i]:rows[i] + (j - i)].fill_(slots[i])
             with self.adapters.active(names[i]), ops.batch_invariant():
                 self._admit_runs(rows[i:j], prompts[i:j], tags[i:j], None if resolved is None else resolved[i:j],
-                                 None, None if pens is None else pens[i:j])
+                                 None, None if pens is None else pens[i:j], None if stops is None else stops[i:j])
             for r in range(i, j):
                 self.row_adapter[rows[r]] = names[r]
             i = j
 
-    def _admit_runs(self, rows, prompts, tags, resolved=None, drafts=None, pens=None):
+    def _admit_runs(self, rows, prompts, tags, resolved=None, drafts=None, pens=None, stops=None):
         g = self.gen
         i = 0
         while i < len(rows):
@@ -1266,6 +1455,9 @@ class ContinuousBatcher:
             g.active[b0:b0 + n].fill_(1)
             if resolved is not None:
                 g.rowp.write(b0, resolved[i:j])
+            if stops is not None:
+                # the row's own stops and a fresh scan state, before _emit scans the first token
+                g.stopp.write(b0, stops[i:j])
             if pens is not None:
                 # the prefill logits are penalised over the prompt alone (no generated token yet); the
                 # first sampled token then sits at slot S, where the first decode step appends it again
@@ -1290,6 +1482,8 @@ class ContinuousBatcher:
                 self.rows[b0 + r] = (tags[i + r], len(grp[r]), self.steps)
                 if resolved is not None:
                     self.row_seed[b0 + r] = resolved[i + r][4]
+                if stops is not None:
+                    self.row_stops[b0 + r] = stops[i + r]
             i = j
 
     def step(self, n: int = 1):
@@ -1323,9 +1517,23 @@ class ContinuousBatcher:
                 # the stream is already drained by the reads above: two more small copies, no new wait
                 stats = g._lk.row_stats.index_select(0, idx).cpu().tolist()
                 self.lookup_totals = tuple(int(c) for c in g._lk.counters.tolist())
-            for b, n, t, lp, (ls, la) in zip(done, lens, toks, lps, stats):
+            hits = [(-1, 0)] * len(done)
+            if self.stops:
+                hits = list(zip(g.stopp.stop_hit.index_select(0, idx).cpu().tolist(),
+                                g.stopp.stop_at.index_select(0, idx).cpu().tolist()))
+            for b, n, t, lp, (ls, la), (hit, at) in zip(done, lens, toks, lps, stats, hits):
                 tag, S, s0 = self.rows.pop(b)
-                out.append(FinishedRow(tag, t[:n].tolist(), lp[:n].tolist(), S, self.steps - s0,
-                                       self.row_seed.pop(b, None), self.row_adapter.pop(b, None), ls, la))
+                toks_b = t[:n].tolist()
+                strings, ids = self.row_stops.pop(b, ((), ()))
+                reason, what, keep = "length", None, None
+                if hit >= 0:
+                    reason, keep = "stop", at
+                    what = strings[hit].decode("utf-8", "replace") if hit < ops.STOP_MAX_STR else \
+                        ids[hit - ops.STOP_MAX_STR]
+                elif toks_b and toks_b[-1] in self.eos_list:
+                    reason = "eos"
+                out.append(FinishedRow(tag, toks_b, lp[:n].tolist(), S, self.steps - s0,
+                                       self.row_seed.pop(b, None), self.row_adapter.pop(b, None), ls, la,
+                                       reason, what, keep))
                 self.free.append(b)
         return out

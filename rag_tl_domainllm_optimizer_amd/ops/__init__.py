@@ -13,8 +13,9 @@ from .attention import (  # noqa: F401
     verify_step_attention,
 )
 from .misc import (embedding, gae, ivf_scan, ppo_advantages, pool_normalize, ppo_loss, row_dot, sample, sample_rows, segment_mean,  # noqa: F401
-                   swiglu, token_logprobs, topk, lookup_accept, lookup_draft, logit_rows_penalty)
+                   swiglu, token_logprobs, topk, lookup_accept, lookup_draft, logit_rows_penalty, stop_rows, TokenBytes)
 from .reference import LOGIT_ROWS_MAX_BIAS, LOGIT_ROWS_MAX_SEQ  # noqa: F401
+from .reference import STOP_MAX_ENTRY, STOP_MAX_LEN, STOP_MAX_STR, STOP_MAX_TOK  # noqa: F401
 from .optim import FlatParams, FusedAdamW, MixedFlatParams, flat_params  # noqa: F401
 from .fp8 import Fp8Cache, dequantize_fp8, gemm_fp8, quantize_fp8  # noqa: F401
 from .fp4 import Fp4Cache, dequantize_mxfp4, fp4_supported, quantize_mxfp4  # noqa: F401

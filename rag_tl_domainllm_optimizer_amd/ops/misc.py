@@ -200,6 +200,82 @@ def logit_rows_penalty(logits, hist, tok_in, kv_len, kv_start, gen_len, active, 
     return logits
 
 
+class TokenBytes:
+    """The vocabulary byte table on a device: entry t is what token t adds to the decoded text
+    (``Tokenizer.token_bytes``), ``offsets`` int32 [V + 1] into ``blob`` uint8 [total], and
+    ``strip_first_space``: the stream text of a token list is the concatenation of its entries
+    without one leading space when the flag is set and the concatenation starts with one. Built once
+    per engine; ValueError for a table that is not monotone or whose longest entry exceeds the
+    ``STOP_MAX_ENTRY`` bytes ``stop_rows_kernel`` stages per token."""
+
+    def __init__(self, offsets, blob, strip_first_space: bool, device=None, vocab_size: Optional[int] = None):
+        offsets = torch.as_tensor(offsets, dtype=torch.int32).flatten().cpu()
+        blob = torch.as_tensor(blob, dtype=torch.uint8).flatten().cpu()
+        if offsets.numel() < 2 or int(offsets[0]) != 0 or int(offsets[-1]) != blob.numel():
+            raise ValueError("token byte table: offsets must run from 0 to the blob's length over V + 1 entries")
+        lens = offsets[1:] - offsets[:-1]
+        if bool((lens < 0).any()):
+            raise ValueError("token byte table: offsets must not decrease")
+        longest = int(lens.max())
+        if longest > ref.STOP_MAX_ENTRY:
+            t = int(lens.argmax())
+            raise ValueError(f"token byte table: token {t} decodes to {longest} bytes, more than the "
+                             f"{ref.STOP_MAX_ENTRY} bytes per token the stop kernel stages; stop strings are not "
+                             f"available with this vocabulary")
+        V = offsets.numel() - 1
+        if vocab_size is not None and vocab_size > V:
+            # ids the tokenizer does not know decode to nothing
+            offsets = torch.cat([offsets, offsets[-1:].expand(vocab_size - V)])
+        elif vocab_size is not None and vocab_size < V:
+            raise ValueError(f"token byte table: {V} entries for a vocabulary of {vocab_size}")
+        self.vocab_size = offsets.numel() - 1
+        self.strip_first_space = bool(strip_first_space)
+        self.device = torch.device(device) if device is not None else torch.device("cpu")
+        self.offsets = offsets.contiguous().to(self.device)
+        # one spare byte: an empty blob still has a data pointer
+        self.blob = (blob if blob.numel() else torch.zeros(1, dtype=torch.uint8)).contiguous().to(self.device)
+        # host copies: the stream text of a finished row (``stream_text``)
+        self._offsets_host = offsets.tolist()
+        self._blob_host = bytes(blob.tolist())
+        self.source = None  # the tokenizer the table was built from (``from_tokenizer``)
+
+    @property
+    def key(self):
+        """What a captured step that reads this table is tied to: its device memory and scalars. The
+        step keeps the tensors alive, so no other table can show the same key while the step exists."""
+        return self.offsets.data_ptr(), self.blob.data_ptr(), self.strip_first_space, self.vocab_size
+
+    def stream_text(self, ids) -> bytes:
+        """The stream text of an id list: the entries' bytes with the start rule applied"""
+        o, V = self._offsets_host, self.vocab_size
+        raw = b"".join(self._blob_host[o[t]:o[t + 1]] for t in ids if 0 <= t < V)
+        return raw[1:] if (self.strip_first_space and raw[:1] == b" ") else raw
+
+    @classmethod
+    def from_tokenizer(cls, tokenizer, device=None, vocab_size: Optional[int] = None) -> "TokenBytes":
+        offsets, blob, strip = tokenizer.token_bytes()
+        tb = cls(offsets, blob, strip, device, vocab_size)
+        tb.source = tokenizer
+        return tb
+
+
+def stop_rows(out_tokens, gen_len, active, table: TokenBytes, n_stop, stop_len, stop_bytes, n_stop_tok, stop_tok, seen,
+              nbytes, stop_hit, stop_at):
+    """Per-request stop strings and stop token ids over the rows' new tokens ``out_tokens[b,
+    seen[b]:gen_len[b]]`` (int64 [B, T]), in place on ``gen_len`` i32 [B], ``active`` u8 [B] and the
+    row state (``stop_rows_kernel``, one wave per row; its twin and the rule:
+    ``ops.reference.stop_rows``). ``n_stop`` i32 [B], ``stop_len`` i32 [B, 4], ``stop_bytes`` u8
+    [B, 4, 32], ``n_stop_tok`` i32 [B], ``stop_tok`` i32 [B, 8], ``seen`` / ``nbytes`` / ``stop_hit``
+    / ``stop_at`` i32 [B]: per-row tensors on the tokens' device, so a captured graph sees new values
+    on replay."""
+    args = (out_tokens, gen_len, active, table.offsets, table.blob, table.strip_first_space, n_stop, stop_len,
+            stop_bytes, n_stop_tok, stop_tok, seen, nbytes, stop_hit, stop_at)
+    if on_gpu(out_tokens):
+        native().stop_rows(*args)
+    else:
+        ref.stop_rows(*args)
+
+
 # ------------------------------------------------- prompt-lookup speculative decoding bookkeeping
 def lookup_accept(sampled, logp, inp, n_draft, out_tokens, out_logp, hist, active, kv_len, pos, attn_len, kv_start,
                   gen_len, step, rng_offset, counters, eos_ids, row_max_new=None, row_stats=None):

@@ -440,6 +440,71 @@ def lookup_draft(hist, kv_len, kv_start, active, ngram, pad_id, inp, n_draft, ro
         n_draft[b] = avail
 
 
+STOP_MAX_STR = 4      # stop strings per row
+STOP_MAX_LEN = 32     # bytes per stop string
+STOP_MAX_TOK = 8      # stop token ids per row
+STOP_MAX_ENTRY = 256  # bytes of the longest vocabulary entry stop_rows_kernel stages
+
+
+def stop_rows(out_tokens, gen_len, active, offsets, blob, strip_first_space, n_stop, stop_len, stop_bytes, n_stop_tok,
+              stop_tok, seen, nbytes, stop_hit, stop_at):
+    """Twin of stop_rows_kernel (in place on ``gen_len``, ``active``, ``seen``, ``nbytes``,
+    ``stop_hit``, ``stop_at``). Row b's generated tokens are ``out_tokens[b, :gen_len[b]]``; the
+    concatenation of their entries in the byte table (``offsets`` [V + 1], ``blob``) is the raw
+    stream, and the stream text is the raw stream without one leading space when
+    ``strip_first_space`` is set and it starts with one. Tokens ``seen[b]`` .. ``gen_len[b]`` are
+    new. They are taken one at a time: the first token that is one of the row's stop ids, or inside
+    whose bytes an occurrence of one of its stop strings ends, finishes the row. Among the matches
+    completed by that token the smallest start wins (a stop id is a zero-length match where the token
+    begins and wins over a string at the same offset; ties between strings go to the lower index); a
+    match may not begin inside the stripped space. A hit writes ``stop_hit`` (0..3 the string, 4 + j
+    stop id j), ``stop_at`` (the match start in the stream text), ``active = 0`` and ``gen_len`` =
+    that token's index + 1; no hit writes ``seen = gen_len`` and ``nbytes`` = the raw bytes scanned.
+    Rows with nothing new, without stops, or already stopped are left alone."""
+    B, T = out_tokens.shape
+    V = offsets.numel() - 1
+    offs = offsets.tolist()
+    raw_blob = bytes(blob.tolist())
+    for b in range(B):
+        ns = min(max(int(n_stop[b]), 0), STOP_MAX_STR)
+        nt = min(max(int(n_stop_tok[b]), 0), STOP_MAX_TOK)
+        gl, s = min(int(gen_len[b]), T), max(int(seen[b]), 0)
+        if s >= gl or (ns == 0 and nt == 0) or int(stop_hit[b]) >= 0:
+            continue
+        strings = [bytes(stop_bytes[b, i, :min(max(int(stop_len[b, i]), 0), STOP_MAX_LEN)].tolist()) for i in range(ns)]
+        ids = [int(stop_tok[b, j]) for j in range(nt)]
+        toks = out_tokens[b, :gl].tolist()
+        raw, begin = b"", []
+        for t in toks:
+            begin.append(len(raw))
+            if 0 <= t < V:
+                raw += raw_blob[offs[t]:offs[t + 1]][:STOP_MAX_ENTRY]
+        begin.append(len(raw))
+        skip = 1 if (strip_first_space and raw[:1] == b" ") else 0
+        hit = None
+        for n in range(s, gl):
+            cands = [(begin[n], j) for j, t in enumerate(ids) if toks[n] == t][:1]
+            for i, st in enumerate(strings):
+                if not st:
+                    continue
+                # the first occurrence that ends inside token n's bytes
+                p = raw.find(st, max(skip, begin[n] + 1 - len(st)), begin[n + 1])
+                if p >= 0:
+                    cands.append((p, STOP_MAX_TOK + i))
+            if cands:
+                hit = (n,) + min(cands)
+                break
+        if hit is None:
+            seen[b] = gl
+            nbytes[b] = len(raw)
+        else:
+            n, start, kind = hit
+            stop_hit[b] = STOP_MAX_STR + kind if kind < STOP_MAX_TOK else kind - STOP_MAX_TOK
+            stop_at[b] = max(start - skip, 0)
+            active[b] = 0
+            gen_len[b] = n + 1
+
+
 LOGIT_ROWS_MAX_SEQ = 4096  # history slots the logit_rows_penalty kernel stages per row
 LOGIT_ROWS_MAX_BIAS = 16
 

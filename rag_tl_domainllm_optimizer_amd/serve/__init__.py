@@ -8,7 +8,11 @@ with prompt-lookup decoding (``serve --eval.lookup_tokens=3``; GET /health repor
 the body may also carry ``lookup_tokens`` in 0..K, the request's own draft length. With
 ``logit_penalties`` (config ``serve.logit_penalties``, needs ``per_request_sampling``) the body may
 also carry ``repetition_penalty``, ``presence_penalty``, ``frequency_penalty`` and ``logit_bias``, a
-JSON object of token id (as a string) -> bias, as in the OpenAI API.
+JSON object of token id (as a string) -> bias, as in the OpenAI API. With ``stop_sequences`` (config
+``serve.stop_sequences``, needs ``per_request_sampling``) the body may also carry ``stop`` (a string or
+a list of at most 4 strings of 1..32 UTF-8 bytes) and ``stop_token_ids`` (at most 8); the answer ends
+where the first of them begins, and ``timings["finish_reason"]`` says why the answer ended
+(``"stop"``, ``"eos"`` or ``"length"``).
 
 Concurrent requests are batched: the async handler awaits a future while one worker thread owns the
 GPU — by default ``serve.continuous.ContinuousEngine`` (requests join the running decode batch
@@ -23,6 +27,7 @@ from .continuous import ContinuousEngine  # noqa: F401
 
 SAMPLING_FIELDS = ("temperature", "top_k_tokens", "top_p", "do_sample", "seed", "max_new_tokens", "lookup_tokens")
 PENALTY_FIELDS = ("repetition_penalty", "presence_penalty", "frequency_penalty", "logit_bias")
+STOP_FIELDS = ("stop", "stop_token_ids")
 
 
 def request_sampling(q, max_new_tokens: Optional[int] = None, lookup_tokens: Optional[int] = None,
@@ -34,20 +39,20 @@ def request_sampling(q, max_new_tokens: Optional[int] = None, lookup_tokens: Opt
     lie in (None: not checked here)."""
     from ..generation import RequestSampling
 
-    vals = {f: getattr(q, f, None) for f in SAMPLING_FIELDS + PENALTY_FIELDS}
+    vals = {f: getattr(q, f, None) for f in SAMPLING_FIELDS + PENALTY_FIELDS + STOP_FIELDS}
     if all(v is None for v in vals.values()):
         return None
     rs = RequestSampling(temperature=vals["temperature"], top_k=vals["top_k_tokens"], top_p=vals["top_p"],
                          do_sample=vals["do_sample"], seed=vals["seed"], max_new_tokens=vals["max_new_tokens"],
-                         lookup_tokens=vals["lookup_tokens"], **{f: vals[f] for f in PENALTY_FIELDS})
+                         lookup_tokens=vals["lookup_tokens"], **{f: vals[f] for f in PENALTY_FIELDS + STOP_FIELDS})
     rs.validate(max_new_tokens, lookup_tokens, vocab)
     return rs
 
 
 def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, per_request_sampling: bool = False,
-               adapters=None, logit_penalties: bool = False):
+               adapters=None, logit_penalties: bool = False, stop_sequences: bool = False):
     import asyncio
-    from typing import Dict
+    from typing import Dict, List, Union
 
     from fastapi import FastAPI, HTTPException
     from pydantic import BaseModel
@@ -58,11 +63,13 @@ def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, pe
         raise ValueError("per-request adapters need continuous batching (continuous=True)")
     if logit_penalties and not per_request_sampling:
         raise ValueError("logit_penalties needs per_request_sampling (penalties are per-request settings)")
-    if logit_penalties:
-        engine = ContinuousEngine(pipeline, per_request_sampling=True, adapters=adapters, logit_penalties=True)
+    if stop_sequences and not per_request_sampling:
+        raise ValueError("stop_sequences needs per_request_sampling (stops are per-request settings)")
+    if continuous:
+        engine = ContinuousEngine(pipeline, per_request_sampling=per_request_sampling, adapters=adapters,
+                                  logit_penalties=bool(logit_penalties), stop_sequences=bool(stop_sequences))
     else:
-        engine = ContinuousEngine(pipeline, per_request_sampling=per_request_sampling, adapters=adapters) \
-            if continuous else BatchingEngine(pipeline, max_wait_s=max_wait_s)
+        engine = BatchingEngine(pipeline, max_wait_s=max_wait_s)
     vocab = getattr(getattr(getattr(pipeline, "gen", None), "cfg", None), "vocab_size", None)
     app = FastAPI(title="rag-tl-domainllm-optimizer-amd")
     app.state.engine = engine
@@ -84,13 +91,16 @@ def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, pe
         presence_penalty: Optional[float] = None
         frequency_penalty: Optional[float] = None
         logit_bias: Optional[Dict[str, float]] = None  # token id (as a string) -> bias in [-100, 100]
+        # servers with serve.stop_sequences
+        stop: Optional[Union[str, List[str]]] = None
+        stop_token_ids: Optional[List[int]] = None
 
     @app.get("/health")
     def health():
         return {"status": "ok", "docs": len(pipeline.docs), "max_batch": pipeline.max_batch,
                 "batching": "continuous" if continuous else "dynamic", "per_request_sampling": per_request_sampling,
                 "adapters": adapters.loaded() if adapters is not None else [], "lookup_tokens": engine_k,
-                "logit_penalties": bool(logit_penalties)}
+                "logit_penalties": bool(logit_penalties), "stop_sequences": bool(stop_sequences)}
 
     @app.get("/stats")
     def stats():
@@ -106,6 +116,9 @@ def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, pe
         if rs is not None and rs.has_penalties and per_request_sampling and not logit_penalties:
             raise HTTPException(status_code=400, detail="logit penalties in the request need the server flag "
                                                         "serve.logit_penalties (off on this server)")
+        if rs is not None and rs.has_stops and per_request_sampling and not stop_sequences:
+            raise HTTPException(status_code=400, detail="stop / stop_token_ids in the request need the server flag "
+                                                        "serve.stop_sequences (off on this server)")
         if rs is not None and not per_request_sampling:
             raise HTTPException(status_code=400, detail="sampling settings in the request need the server flag "
                                                         "serve.per_request_sampling (off on this server)")
@@ -130,7 +143,7 @@ def create_app(pipeline, max_wait_s: float = 0.004, continuous: bool = False, pe
 
 def serve(cfg, host: str = "127.0.0.1", port: int = 8000, max_batch: int = 16, max_wait_s: float = 0.004,
           continuous: bool = True, per_request_sampling: Optional[bool] = None, adapters=None,
-          logit_penalties: Optional[bool] = None):
+          logit_penalties: Optional[bool] = None, stop_sequences: Optional[bool] = None):
     import uvicorn
 
     from ..cli import apply_fp4, build_stack
@@ -150,6 +163,8 @@ def serve(cfg, host: str = "127.0.0.1", port: int = 8000, max_batch: int = 16, m
         per_request_sampling = cfg.serve.per_request_sampling
     if logit_penalties is None:
         logit_penalties = cfg.serve.logit_penalties
+    if stop_sequences is None:
+        stop_sequences = cfg.serve.stop_sequences
     # per-request adapters: serve.adapters {name: PEFT directory}, plus / overridden by ``adapters``
     named = dict(getattr(cfg.serve, "adapters", None) or {})
     named.update(adapters or {})
@@ -167,5 +182,5 @@ def serve(cfg, host: str = "127.0.0.1", port: int = 8000, max_batch: int = 16, m
         bank = AdapterBank(st["policy"], slots=max(8, len(named)), r_max=next(r for r in (8, 16, 32, 64) if r >= max(ranks)))
         for name, path in named.items():
             bank.load(name, path)
-    uvicorn.run(create_app(rag, max_wait_s, continuous, per_request_sampling, bank, logit_penalties), host=host,
-                port=port)
+    uvicorn.run(create_app(rag, max_wait_s, continuous, per_request_sampling, bank, logit_penalties, stop_sequences),
+                host=host, port=port)

@@ -36,7 +36,8 @@ class BatchingEngine:
             # a request group runs to completion under the pipeline's one SamplingParams
             raise ValueError("BatchingEngine does not support per-request sampling settings; use "
                              "ContinuousEngine(per_request_sampling=True) (and logit_penalties=True for "
-                             "repetition_penalty, presence_penalty, frequency_penalty and logit_bias)")
+                             "repetition_penalty, presence_penalty, frequency_penalty and logit_bias, stop_sequences=True "
+                             "for stop and stop_token_ids)")
         if self._closed:
             raise RuntimeError("BatchingEngine is closed")
         fut: cf.Future = cf.Future()

@@ -31,6 +31,11 @@ accepted draft tokens); ``stats`` keeps the running totals ``lookup_steps`` / ``
 ``logit_penalties=True`` (needs ``per_request_sampling``; not with prompt-lookup decoding): a request's
 ``RequestSampling`` may also carry ``repetition_penalty``, ``presence_penalty``, ``frequency_penalty``
 and ``logit_bias`` (``ContinuousBatcher(penalties=True)``).
+
+``stop_sequences=True`` (needs ``per_request_sampling``): a request's ``RequestSampling`` may also
+carry ``stop`` and ``stop_token_ids`` (``ContinuousBatcher(stops=True)``; the engine builds the
+vocabulary byte table from the pipeline's tokenizer). The decoded answer is cut where the match
+begins, and every answer's ``timings`` gain ``finish_reason`` (``"stop"``, ``"eos"`` or ``"length"``).
 """
 from __future__ import annotations
 
@@ -51,7 +56,11 @@ from ..rag.prompt import extract_answer
 
 class ContinuousEngine:
     def __init__(self, pipeline, chunk: int = 4, per_request_sampling: bool = False, adapters=None,
-                 logit_penalties: bool = False):
+                 logit_penalties: bool = False, stop_sequences: bool = False):
+        if stop_sequences and not per_request_sampling:
+            raise ValueError("stop_sequences needs per_request_sampling=True (stops are per-request settings)")
+        self.stop_sequences = bool(stop_sequences)
+        self._token_bytes = None  # the vocabulary byte table (stop_sequences), built by the worker
         if logit_penalties and not per_request_sampling:
             raise ValueError("logit_penalties needs per_request_sampling=True (penalties are per-request settings)")
         self.logit_penalties = bool(logit_penalties)
@@ -93,6 +102,8 @@ class ContinuousEngine:
                 raise ValueError("per-request sampling settings need ContinuousEngine(per_request_sampling=True)")
             if sampling.has_penalties and not self.logit_penalties:
                 raise ValueError("logit penalty settings in the request need ContinuousEngine(logit_penalties=True)")
+            if sampling.has_stops and not self.stop_sequences:
+                raise ValueError("stop / stop_token_ids in the request need ContinuousEngine(stop_sequences=True)")
             sampling.validate(self.pipeline.sampling.max_new_tokens, self.lookup_tokens,
                               self.pipeline.gen.cfg.vocab_size)
         with self._lock:
@@ -178,7 +189,13 @@ class ContinuousEngine:
             m = r.tag
             if m["fut"].done():  # failed or cancelled elsewhere: nothing to deliver
                 continue
-            text = extract_answer(p.tok.decode(r.tokens))
+            if r.text_bytes is not None:
+                # the stream text from the byte table, cut where the match begins: a cut (or a stop
+                # token) inside a multi-byte character decodes with replacement instead of raising
+                text = self._token_bytes.stream_text(r.tokens)[:r.text_bytes].decode("utf-8", "replace")
+            else:
+                text = p.tok.decode(r.tokens)
+            text = extract_answer(text)
             rs0, st0 = m["rows0"]
             steps = self.stats["steps"] - st0
             tim = {"queue_s": m["t_admit"] - m["t_submit"], "retrieve_s": m["retrieve_s"],
@@ -189,6 +206,8 @@ class ContinuousEngine:
                 tim["seed"] = r.seed
             if self.adapters is not None:
                 tim["adapter"] = r.adapter
+            if self.stop_sequences:
+                tim["finish_reason"] = r.finish_reason
             if r.lookup_steps is not None:
                 tim["lookup_steps"], tim["lookup_accepted"] = r.lookup_steps, r.lookup_accepted
             m["fut"].set_result(RagAnswer(m["query"], text, m["doc_ids"], m["docs"], m["scores"], tim))
@@ -197,19 +216,22 @@ class ContinuousEngine:
     def _loop(self):
         p = self.pipeline
         try:
-            if self.lookup_tokens > 0:
-                # the batcher takes lookup as its own keyword; its SamplingParams carry none
-                cb = ContinuousBatcher(p.gen, dataclasses.replace(p.sampling, lookup_tokens=0),
-                                       pad_id=p.tok.pad_token_id, eos_ids=[p.tok.eos_token_id],
-                                       per_request=self.per_request_sampling, adapters=self.adapters,
-                                       lookup_tokens=self.lookup_tokens, lookup_ngram=self.lookup_ngram,
-                                       penalties=self.logit_penalties)
-            elif self.logit_penalties:
-                cb = ContinuousBatcher(p.gen, p.sampling, pad_id=p.tok.pad_token_id, eos_ids=[p.tok.eos_token_id],
-                                       per_request=True, adapters=self.adapters, penalties=True)
-            else:
-                cb = ContinuousBatcher(p.gen, p.sampling, pad_id=p.tok.pad_token_id, eos_ids=[p.tok.eos_token_id],
-                                       per_request=self.per_request_sampling, adapters=self.adapters)
+            if self.stop_sequences:
+                from ..ops import TokenBytes
+
+                # one table per generator and tokenizer: engines that follow each other on a pipeline
+                # share it, and with it the captured steps that read it
+                tb = p.gen.token_bytes
+                if not (isinstance(tb, TokenBytes) and tb.source is p.tok and tb.device == p.gen.device):
+                    tb = TokenBytes.from_tokenizer(p.tok, p.gen.device, p.gen.cfg.vocab_size)
+                self._token_bytes = tb
+            # the batcher takes lookup as its own keyword; its SamplingParams carry none
+            cb = ContinuousBatcher(p.gen, dataclasses.replace(p.sampling, lookup_tokens=0),
+                                   pad_id=p.tok.pad_token_id, eos_ids=[p.tok.eos_token_id],
+                                   per_request=self.per_request_sampling, adapters=self.adapters,
+                                   lookup_tokens=self.lookup_tokens, lookup_ngram=self.lookup_ngram,
+                                   penalties=self.logit_penalties, stops=self.stop_sequences,
+                                   token_bytes=self._token_bytes)
         except BaseException as e:  # noqa: BLE001
             self._init_error = e
             self._ready.set()

@@ -167,6 +167,17 @@ class Tokenizer:
     def batch_decode(self, seqs, skip_special_tokens: bool = True) -> List[str]:
         return [self.decode(s, skip_special_tokens) for s in seqs]
 
+    def token_bytes(self):
+        """The vocabulary byte table: ``(offsets int32 [V + 1], blob uint8 [total], strip_first_space)``.
+        Entry t = ``blob[offsets[t]:offsets[t + 1]]`` is what token t adds to the decoded text (nothing
+        for a special token). For any id list, the concatenation of the entries, with one leading
+        space removed when ``strip_first_space`` is set and the concatenation starts with one, is the
+        UTF-8 encoding of ``decode(ids, skip_special_tokens=True)``."""
+        offsets, blob = self._impl.token_bytes_table()
+        data = torch.frombuffer(bytearray(blob), dtype=torch.uint8).clone() if blob else \
+            torch.zeros(0, dtype=torch.uint8)
+        return torch.tensor(offsets, dtype=torch.int32), data, bool(self._impl.strip_first_space())
+
     def token_to_id(self, t: str) -> int:
         return int(self._impl.token_to_id(t))
 
